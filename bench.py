@@ -19,9 +19,13 @@ touches the GPU); every rank solves its contiguous shard with no collective in
 the data path; timings are max-reduced over ranks.  Scaling is "strong": the
 1 M batch is fixed as N grows (`--batch B` gives weak scaling at B per GPU).
 
-Also reported:
+A plain run sets up, settles, warms up, times the steps and prints one JSON
+line; `--dump-outputs DIR` also writes what the last timed step computed (a
+fixed seeded sample of the QPs) as DIR/<name>.npy.  Also in the line:
   roofline     -- algorithmic HBM bytes per launch / mean kernel time (HIP
                   events on the launch stream) vs 8 TB/s
+Only with `--full` (legs of their own, null otherwise), beside the box fast
+path, the dense family, the pipelined and the sustained legs:
   cpu_baseline -- the reference's own qp_solvers.c admm() (compiled from
                   /root/reference by oracle/Makefile, box +-10 compiled in) on
                   a sample of the same QPs, one forked process per core of
@@ -260,6 +264,45 @@ def relaunch(n: int) -> int:
     return subprocess.call(cmd)
 
 
+# --------------------------------------------------------------------------- output dump
+DUMP_BYTES = 32 << 20  # --dump-outputs writes at most this much over all ranks (n=16, m=32: 416 B per QP)
+
+
+def dump_sample(total: int, seed: int, n: int, m: int):
+    """The QP indices --dump-outputs writes: every QP of a batch whose dump
+    fits DUMP_BYTES, else as many distinct indices as fit, drawn by a
+    generator seeded with the run's seed (the same for the same arguments),
+    ascending."""
+    import numpy as np
+    k = max(1, DUMP_BYTES // (8 * (n + m + (m + 31) // 32 + 3)))
+    if total <= k:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, sol, start: int, total: int, seed: int, rank: int, world: int) -> None:
+    """Write the sampled rows of the solve's outputs that fall in this rank's
+    shard [start, start + B) as out_dir/<name>.npy (<name>.rank<r>.npy when
+    there are several ranks): x and lam as they are (float64), the active-set
+    words (as unsigned), status, iters and the sampled global QP indices
+    (qp_index) as float64, all exact."""
+    import numpy as np
+    import torch
+    B = sol.x.shape[0]
+    idx = dump_sample(total, seed, sol.x.shape[1], sol.lam.shape[1])
+    idx = idx[(idx >= start) & (idx < start + B)]
+    rows = torch.from_numpy(idx - start).to(sol.x.device)
+    arrays = {"qp_index": idx.astype(np.float64),
+              "x": sol.x[rows].cpu().numpy(),
+              "lam": sol.lam[rows].cpu().numpy(),
+              "active": (sol.active[rows].cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype(np.float64),
+              "status": sol.status[rows].cpu().numpy().astype(np.float64),
+              "iters": sol.iters[rows].cpu().numpy().astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 # --------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -274,6 +317,15 @@ def main():
     ap.add_argument("--n", type=int, default=16)
     ap.add_argument("--family", choices=["box", "dense"], default="box")
     ap.add_argument("--seed", type=int, default=20261015)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the CPU baseline, the like-for-like "
+                         "replica rows, the box fast path, the dense family, the pipelined and the sustained "
+                         "legs (each still switched by its own option below); without it a run sets up, "
+                         "settles, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (x, lam, active, "
+                         "status, iters of a fixed seeded sample of the QPs, and the sampled QP indices) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=0, help="0 = this process's CPU share")
     ap.add_argument("--cpu-sample", type=int, default=4096)
@@ -309,7 +361,8 @@ def main():
     # before this process initialises the GPU.  The sample is the first
     # cpu_sample QPs of the GPU batch, restated on the CPU (oracle.family_generate).
     cpu, cpu_newton = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.family == "box" and args.n == 16:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.family == "box"
+            and args.n == 16):
         procs = args.cpu_procs or cpu_share()
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle  # CPU restatement of qpb_generate: the first QPs of the GPU batch
@@ -431,11 +484,14 @@ def main():
                       "check": "each rank's integer digest of its shard == the digest of its rows on rank 0"}
         del full
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol, start, total_B, args.seed, rank, world)
+
     # pipelined leg, outside the timed steps: K batches over S streams, each
     # stream with its own outputs; barrier + max over ranks as above.  The
     # line's value stays the single-stream one (one pass per step, in order).
     pipelined = None
-    if args.pipeline_streams > 1:
+    if args.full and args.pipeline_streams > 1:
         S = args.pipeline_streams
         pstreams = [torch.cuda.Stream(device=device) for _ in range(S)]
         psols = [qpb.solve(H, f, A, b, stream=ps) for ps in pstreams]
@@ -456,7 +512,7 @@ def main():
     # about --sustain-seconds (launched 20 at a time, the host checking the
     # clock between groups), barrier + max over ranks as above
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         barrier()
         ts = time.perf_counter()
         ks = 0
@@ -484,7 +540,7 @@ def main():
 
     # like-for-like rows (N = 1): the reference's Newton and ADMM as GPU replicas
     like = None
-    if rank == 0 and world == 1 and n == 16 and args.family == "box" and args.ref_batch > 0:
+    if args.full and rank == 0 and world == 1 and n == 16 and args.family == "box" and args.ref_batch > 0:
         Br = min(args.ref_batch, B)
         x0 = torch.zeros((Br, n), dtype=torch.float64, device=device)
         like = {"qps": Br, "inputs": "the first QPs of the bench batch (P = H, q = f), x0 = 0, ADMM box +-10"}
@@ -506,7 +562,7 @@ def main():
     # the box fast path (A = [I; -I] implicit, reported
     # separately): the same QPs through qpb_solve_box, outside the timed steps
     box = None
-    if rank == 0 and world == 1 and n <= 16 and args.family == "box" and args.box_reps > 0:
+    if args.full and rank == 0 and world == 1 and n <= 16 and args.family == "box" and args.box_reps > 0:
         ub = b[:, :n].contiguous()
         lb = (-b[:, n:]).contiguous()
         bsol = qpb.solve_box(H, f, lb, ub, stream=stream)
@@ -530,7 +586,7 @@ def main():
     # the dense family (random normalised A rows) at the same
     # batch: the same kernel on QPs whose constraints are not a box in disguise
     dense = None
-    if rank == 0 and world == 1 and n <= 16 and args.family == "box" and args.dense_reps > 0:
+    if args.full and rank == 0 and world == 1 and n <= 16 and args.family == "box" and args.dense_reps > 0:
         Hd, fd, Ad, bd = qpb.generate(n, B, args.seed, family="dense", shift=1.0, box=10.0, device=device)
         dsol = qpb.solve(Hd, fd, Ad, bd, stream=stream)
         dev_ = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))

@@ -99,6 +99,22 @@ def test_cpu_run_before_gpu_init_is_allowed(bench, monkeypatch):
     assert bench.cpu_run("ref_admm_batch", 1, [[0.0]], [0.0], 0.1, 1, lib_name="absent.so") is None
 
 
+def test_dump_sample_is_fixed_and_fits(bench):
+    # --dump-outputs: the same arguments give the same ascending, distinct QP
+    # indices; a small batch is written whole; every BASELINE shape stays under
+    # the 64 MB a dump may take (x n + lam m + mask words + status, iters, index, as fp64)
+    import numpy as np
+    a, b = bench.dump_sample(1 << 20, 20261015, 16, 32), bench.dump_sample(1 << 20, 20261015, 16, 32)
+    assert np.array_equal(a, b) and a.dtype == np.int64
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 1 << 20
+    assert not np.array_equal(a, bench.dump_sample(1 << 20, 1, 16, 32))
+    assert np.array_equal(bench.dump_sample(1000, 5, 16, 32), np.arange(1000))
+    for n, total in ((16, 1 << 20), (16, 65536), (32, 262144), (128, 16384)):
+        m = 2 * n
+        k = len(bench.dump_sample(total, 3, n, m))
+        assert 0 < k <= total and k * 8 * (n + m + (m + 31) // 32 + 3) <= 64 << 20
+
+
 def test_shard_prediction_is_keyed_by_kernel_revision(bench):
     # the N > 1 line's kernel-bound speed-up comes from the committed batch
     # scan only while the scan names a hot-kernel revision of the loaded

@@ -75,7 +75,7 @@ def test_bench_gpus_2_runs_two_ranks(qpb):
     the self-describing `distributed` block."""
     env = dict(os.environ, QPB_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--global-batch", "8192",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--gather", "--sustain-seconds", "0.5"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--gather", "--sustain-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
