@@ -195,12 +195,20 @@ __device__ __forceinline__ void gi_group(
   };
   // row r's constant data from its entries: the violation threshold of the
   // slack, s / |a| < -tol (1 + |b| / |a|), i.e. s < -tol (|a| + |b|) (-inf: a
-  // zero row, never selected), and the zero row's own test 0 <= b
+  // zero row, never selected), and the zero row's own test 0 <= b.  A NaN b is
+  // an absent row, b = +inf (qpb.h), so the threshold is NaN exactly for a row
+  // with a NaN entry or an overflowing norm (nrm2 NaN or inf, neither <= 0):
+  // such a row would fail every comparison and drop out of the problem
+  // unnoticed; it ends the QP as QPB_NUMERICAL before the loop instead.  The
+  // flag is read back from thr[] there (thr must stay NaN-free for every other
+  // input): a bool of its own, live across the factorisation sweep as in
+  // gi_wave and gi_gram, cost 168 VGPRs instead of 162 at MR = 2 and 12 bytes
+  // of scratch in the n = 16, m < 32 form
   auto row_norms = [&](int r, const double (&row)[NL]) {
     const double nrm2 = dot2<NL>([&](int j) { return row[j]; }, [&](int j) { return row[j]; });
     const bool ok = FULL || l + NL * r < m;
-    bl[r] = ok ? bv[r] : 0.0;
-    thr[r] = nrm2 > 0.0 ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
+    bl[r] = ok ? (bv[r] == bv[r] ? bv[r] : kInf) : 0.0;
+    thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
     infeasible_row = infeasible_row || (ok && nrm2 == 0.0 && bl[r] < -feas_tol * (1.0 + __builtin_fabs(bl[r])));
     act[r] = false;
   };
@@ -362,10 +370,14 @@ __device__ __forceinline__ void gi_group(
   int status;
   bool done;
   {
-    // any lane seeing an infeasible zero row marks the whole QP
-    const double bad = row_min(infeasible_row ? -1.0 : 0.0);
+    // any lane seeing an infeasible zero row (-1) or a NaN row (-2) marks the
+    // whole QP
+    bool nan_row = false;
+#pragma unroll
+    for (int r = 0; r < MR; ++r) nan_row = nan_row || thr[r] != thr[r];
+    const double bad = row_min(nan_row ? -2.0 : infeasible_row ? -1.0 : 0.0);
     const bool inf0 = bad < 0.0;
-    status = !spd ? QPB_NOT_SPD : (inf0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
+    status = !spd ? QPB_NOT_SPD : (bad < -1.5 ? QPB_NUMERICAL : inf0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
     done = !spd || inf0;
   }
   bool selecting = true;

@@ -603,18 +603,23 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
       dn2[t] = group_sum(a0 + a1);
     }
     double invn[RT], thr[RT], s[RT];
-    bool zero_bad = false, act[RT];
+    bool zero_bad = false, nan_bad = false, act[RT];
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
       const double nn2 = group_sum(na2[t]);
       invn[t] = nn2 > 0.0 ? rsq(nn2) : 0.0;
       thr[t] = (rowok[t] && nn2 > 0.0) ? -feas_tol * (1.0 + __builtin_fabs(bl[t]) * invn[t]) : -kInf;
       zero_bad = zero_bad || (rowok[t] && nn2 == 0.0 && bl[t] < -feas_tol * (1.0 + __builtin_fabs(bl[t])));
+      // a row of A with a NaN entry or an overflowing norm fails every
+      // comparison and would drop out of the problem unnoticed: QPB_NUMERICAL
+      // instead (qpb.h)
+      nan_bad = nan_bad || (rowok[t] && !(nn2 < kInf));
       act[t] = false;
     }
     if (tid == 0) flags[20] = 0;
     __syncthreads();
-    if (zero_bad && lk == 0) flags[20] = 1;
+    if (zero_bad && lk == 0) atomicOr(&flags[20], 1);
+    if (nan_bad && lk == 0) atomicOr(&flags[20], 2);
     {
       double dy[RT];
       row_dot(E, yb + 34 * lk, dy);  // s = b + D y
@@ -622,7 +627,7 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
       for (int t = 0; t < RT; ++t) s[t] = bl[t] + dy[t];
     }
     __syncthreads();
-    int status = !spd ? QPB_NOT_SPD : (flags[20] ? QPB_INFEASIBLE : QPB_MAX_ITER);
+    int status = !spd ? QPB_NOT_SPD : ((flags[20] & 2) ? QPB_NUMERICAL : flags[20] ? QPB_INFEASIBLE : QPB_MAX_ITER);
     bool done = status != QPB_MAX_ITER;
     clk.tick(2);
     // ------------------------------------------------------- active set
@@ -824,7 +829,11 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
           t1 = red[R_T1 + 2 * w];
           kdrop = (int)red[R_T1 + 2 * w + 1];
         }
-      const double t2 = (nd2 > kDepTol * dd) ? -sp * rcp(nd2) : kBig;
+      // q == n: Q1 spans everything and w = u - Q1^T Q1 u is rounding noise of
+      // the projections (|w| ~ 1e-11 |u| after some tens of updates, above
+      // kDepTol), not a direction: no ADD, as in qpb_gi.hip, where d2 is empty
+      // then.  This also keeps q <= n.
+      const double t2 = (q < n && nd2 > kDepTol * dd) ? -sp * rcp(nd2) : kBig;
       const double tt = t1 < t2 ? t1 : t2;
       if (!(tt < kBig)) {
         status = QPB_INFEASIBLE;

@@ -280,6 +280,9 @@ __global__ __launch_bounds__(64, OCC) void gi_mixed_kernel(
   const float invn = nrm2 > 0.f ? __builtin_amdgcn_rsqf(nrm2) : 0.f;
   const float thr = (rowok && nrm2 > 0.f) ? -kFeas32 * (1.f + __builtin_fabsf(bl) * invn) : -__builtin_huge_valf();
   const bool infeasible0 = wave_any(rowok && nrm2 == 0.f && bl < -kFeas32 * (1.f + __builtin_fabsf(bl)));
+  // a row of A with a NaN entry, or whose norm overflows fp32: left to the
+  // fp64 kernel, which solves the QP or ends it as QPB_NUMERICAL (qpb.h)
+  const bool nan0 = wave_any(rowok && !(nrm2 < __builtin_huge_valf()));
   const float fl = l < n ? (float)fv : 0.f;
 
   // ---- fp32 sweep: H = L L^T, D = A L^{-T}, y = L^{-1} f, s = b + D y
@@ -335,8 +338,8 @@ __global__ __launch_bounds__(64, OCC) void gi_mixed_kernel(
   float um = 0.f, rdg = 0.f, invRd = 0.f;
   int iam = -1;
   bool act = false;
-  int status = !spd ? QPB_NOT_SPD : (infeasible0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
-  bool done = !spd || infeasible0;
+  int status = !spd ? QPB_NOT_SPD : (nan0 ? QPB_NUMERICAL : infeasible0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
+  bool done = !spd || infeasible0 || nan0;
   bool selecting = true;
   int p = 0;
   float up = 0.f;

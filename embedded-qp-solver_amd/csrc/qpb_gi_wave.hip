@@ -252,6 +252,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   const double thr = (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
   const bool infeasible0 =
       wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
+  // a row of A with a NaN entry or an overflowing norm fails every comparison
+  // below and would drop out of the problem unnoticed: QPB_NUMERICAL instead
+  // (qpb.h)
+  const bool nan0 = wave_any(rowok && !(nrm2 < kInf));
   const double fl = l < n ? fv : 0.0;
 
   // ---- H = L L^T, D = A L^{-T}, y = L^{-1} f (right-looking, pivot row by symmetry)
@@ -354,8 +358,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double ninvA = 0.0, ninvB = 0.0;  // -1 / R_jj of positions j = l & 15 and 16 + (l & 15)
   int iam = -1;
   bool act = false;
-  int status = !spd ? QPB_NOT_SPD : (infeasible0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
-  bool done = !spd || infeasible0;
+  int status = !spd ? QPB_NOT_SPD : (nan0 ? QPB_NUMERICAL : infeasible0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
+  bool done = !spd || infeasible0 || nan0;
   bool selecting = true;
   int p = 0;
   double up = 0.0;

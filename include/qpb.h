@@ -34,6 +34,37 @@
  *           active set
  *   status  one int32 per QP (qpb_status); never aborts the batch
  *   iters   one int32 per QP (active-set iterations), may be NULL
+ *           (the other outputs do not depend on it)
+ *
+ * Every element of x, lam, active, status (and iters) of every QP is written
+ * whatever the QP's status, and nothing outside them is.  A QP's outputs
+ * depend on its own inputs only: not on the batch size, on its position, or on
+ * the other QPs of the launch, failed and non-finite ones included.
+ * What the outputs hold when status != QPB_OK (all kernels, qpb_solve_box
+ * included; pinned by tests/test_gpu_status_contract.py):
+ *   QPB_MAX_ITER    iters = max_iter.  lam, active: the dual iterate when the
+ *                   cap was reached -- finite, lam >= 0, zero outside
+ *                   `active`; x = -H^{-1} (f + A^T lam) for that lam, so
+ *                   stationarity holds, primal feasibility in general not.
+ *                   A QP that needs <= max_iter iterations is QPB_OK, with
+ *                   the outputs of an uncapped solve bit for bit.
+ *   QPB_INFEASIBLE  a zero row of A with b < 0 (found in the set-up,
+ *                   iters = 0, lam = 0, active = 0), or a violated row that
+ *                   depends linearly on the active ones and admits no step
+ *                   (found by the iteration, 1 <= iters <= max_iter; lam,
+ *                   active, x as for QPB_MAX_ITER).  Linearly dependent rows
+ *                   of a feasible QP are not an error.
+ *   QPB_NOT_SPD     iters = 0, lam = 0, active = 0; x is unspecified (it may
+ *                   be non-finite).
+ *   QPB_NUMERICAL   a row of A with a NaN entry, or whose squared norm is
+ *                   not finite (found in the set-up: iters = 0, lam = 0,
+ *                   active = 0, x unspecified), or a non-finite x after an
+ *                   otherwise successful iteration.
+ * Non-finite inputs: a NaN or +-Inf anywhere in H or f, or a NaN in a row of
+ * A, gives a status other than QPB_OK (QPB_NOT_SPD takes precedence over
+ * QPB_NUMERICAL, that over QPB_INFEASIBLE).  A NaN in b means the row is
+ * absent, exactly as b = +inf (the box bounds of qpb_solve_box likewise).
+ * feas_tol: row i counts as violated when a_i x - b_i > feas_tol (|a_i| + |b_i|).
  *
  * All array pointers passed to qpb_solve / qpb_ref_solve are DEVICE pointers
  * (hipMalloc'd or torch CUDA tensors) and the call is asynchronous on

@@ -348,6 +348,54 @@ def family_conditioned(seed: int, count: int, n: int, m: int | None = None, box:
     return H, f, A, b
 
 
+def family_shifted(seed: int, count: int, n: int, m: int):
+    """family_conditioned's dense H, f, A (box = 10) with the feasible region
+    moved off the origin: xc ~ U(-20, 20)^n, b = A xc + U(0.1, 1) * 10.  xc is
+    strictly feasible (slack >= 1 on every row), x = 0 in general is not, and
+    about 30 % of the entries of b are negative.  Returns (H, f, A, b, xc); xc
+    is the feasible x0 that active_set_solve needs."""
+    H, f, A, _ = family_conditioned(seed, count, n, m=m, box=10.0, kind="dense")
+    rs = np.random.default_rng([seed, 0x5F1F7])
+    xc = rs.uniform(-20.0, 20.0, size=(count, n))
+    b = np.einsum("bij,bj->bi", A, xc) + rs.uniform(0.1, 1.0, size=(count, m)) * 10.0
+    return H, f, A, b, xc
+
+
+def family_farkas(seed: int, count: int, n: int, m: int, k: int, delta: float = 1.0):
+    """family_shifted with row m-1 replaced by -sum_{i<k} y_i a_i / nr
+    (y ~ U(0.5, 1.5)^k, nr the norm of the sum; k <= m - 1), then the rows
+    permuted per QP.  Two right-hand sides that differ in that row only:
+
+      b_inf   (-sum y_i b_i - delta) / nr: infeasible, the multipliers (y, nr)
+              are a Farkas certificate (A^T c = 0, c >= 0, b^T c = -delta < 0)
+      b_feas  (-sum y_i b_i + sum y_i s_i + delta) / nr with s = b - A xc: the
+              same linearly dependent rows, xc strictly feasible (slack
+              delta / nr on the new row)
+
+    Returns (H, f, A, b_inf, b_feas, xc, cert), cert (count, m) in the permuted
+    row order."""
+    if not 1 <= k <= m - 1:
+        raise ValueError("family_farkas: 1 <= k <= m - 1")
+    H, f, A, b, xc = family_shifted(seed, count, n, m)
+    rs = np.random.default_rng([seed, 0xFA2CA5, k])
+    y = rs.uniform(0.5, 1.5, size=(count, k))
+    row = -np.einsum("bi,bij->bj", y, A[:, :k])
+    nr = np.linalg.norm(row, axis=1)
+    A[:, m - 1] = row / nr[:, None]
+    yb = np.einsum("bi,bi->b", y, b[:, :k])
+    ys = np.einsum("bi,bi->b", y, b[:, :k] - np.einsum("bij,bj->bi", A[:, :k], xc))
+    b_inf, b_feas = b.copy(), b.copy()
+    b_inf[:, m - 1] = (-yb - delta) / nr
+    b_feas[:, m - 1] = (-yb + ys + delta) / nr
+    cert = np.zeros((count, m))
+    cert[:, :k] = y
+    cert[:, m - 1] = nr
+    for i in range(count):
+        perm = rs.permutation(m)
+        A[i], b_inf[i], b_feas[i], cert[i] = A[i, perm], b_inf[i, perm], b_feas[i, perm], cert[i, perm]
+    return H, f, A, b_inf, b_feas, xc, cert
+
+
 # --------------------------------------------------------------------------
 # on-device generators (csrc/qpb_gen.hip), restated for the parity tests
 # --------------------------------------------------------------------------

@@ -191,3 +191,48 @@ def test_oracle_degenerate_vertex_bland():
     assert r.status == 0
     res = O.kkt_residuals(H[None], f[None], A[None], b[None], r.x[None], r.lam[None])
     assert max(float(v.max()) for v in res.values()) <= 1e-9
+
+
+# (n, m) of tests/test_gpu_status_contract.py's routes
+FAMILY_SHAPES = [(16, 32), (7, 14), (5, 3), (32, 64), (20, 33), (48, 96)]
+
+
+def _kkt_worst(H, f, A, b, x, lam):
+    r = O.kkt_residuals(H[None], f[None], A[None], b[None], x[None], lam[None])
+    return max(float(v.max()) for v in r.values())
+
+
+@pytest.mark.parametrize("n,m", FAMILY_SHAPES)
+def test_family_shifted(n, m):
+    """xc is strictly feasible, a fifth or more of b is negative (x = 0 is
+    not feasible: the oracle's default start is refused), and the oracle from
+    xc solves every QP with a KKT certificate."""
+    H, f, A, b, xc = O.family_shifted(900 + n, 16, n, m)
+    assert (b - np.einsum("bij,bj->bi", A, xc) >= 1.0 - 1e-12).all()
+    assert (b < 0).mean() >= 0.2
+    for i in range(len(f)):
+        r = O.active_set_solve(H[i], f[i], A[i], b[i], x0=xc[i])
+        assert r.status == 0, i
+        assert _kkt_worst(H[i], f[i], A[i], b[i], r.x, r.lam) <= 1e-11, i
+    if m >= n:
+        assert any(O.active_set_solve(H[i], f[i], A[i], b[i]).status == 3 for i in range(len(f)))
+
+
+@pytest.mark.parametrize("n,m", FAMILY_SHAPES)
+def test_family_farkas(n, m):
+    """b_inf carries a Farkas certificate (c >= 0, A^T c = 0, b^T c < 0: no x
+    has A x <= b); its twin b_feas differs in one entry, keeps xc strictly
+    feasible and is solved by the oracle with a KKT certificate."""
+    for k in sorted({1, 2, min(n, m - 1), min(n + 1, m - 1)}):
+        H, f, A, b_inf, b_feas, xc, c = O.family_farkas(950 + n, 16, n, m, k)
+        assert (c >= 0).all() and ((c > 0).sum(axis=1) == k + 1).all()
+        Atc = np.einsum("bij,bi->bj", A, c)
+        assert (np.abs(Atc).max(axis=1) <= 1e-12 * np.abs(A).sum(axis=2).max(axis=1)).all()
+        assert (np.einsum("bi,bi->b", b_inf, c) < -0.5).all()
+        assert ((b_inf != b_feas).sum(axis=1) == 1).all()
+        assert (b_feas - np.einsum("bij,bj->bi", A, xc) > 0).all()
+        assert (b_inf < 0).mean() >= 0.2
+        for i in range(len(f)):
+            r = O.active_set_solve(H[i], f[i], A[i], b_feas[i], x0=xc[i])
+            assert r.status == 0, (k, i)
+            assert _kkt_worst(H[i], f[i], A[i], b_feas[i], r.x, r.lam) <= 1e-11, (k, i)
