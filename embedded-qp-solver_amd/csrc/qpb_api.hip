@@ -6,54 +6,11 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
-#include <string.h>
 
 #include "qpb.h"
 #include "qpb_common.h"  // kSectionSlots, kSections
-
-extern "C" hipError_t qpb_launch_gi(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                    const double *b, double *x, double *lam, uint32_t *active,
-                                    int32_t *status, int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_sections(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                             const double *b, double *x, double *lam, uint32_t *active,
-                                             int32_t *status, int32_t *iters, unsigned long long *sections,
-                                             hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_wave_sections(const qpb_desc *d, const double *H, const double *f,
-                                                  const double *A, const double *b, double *x, double *lam,
-                                                  uint32_t *active, int32_t *status, int32_t *iters,
-                                                  unsigned long long *sections, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_wave(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                         const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
-                                         int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_mixed(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                          const double *b, double *x, double *lam, uint32_t *active,
-                                          int32_t *status, int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_gram(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                         const double *b, double *x, double *lam, uint32_t *active,
-                                         int32_t *status, int32_t *iters, unsigned long long *sections,
-                                         hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
-                                        const double *ub, double *x, double *lam, uint32_t *active, int32_t *status,
-                                        int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_gram_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
-                                             const double *ub, double *x, double *lam, uint32_t *active,
-                                             int32_t *status, int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_gi_wave_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
-                                             const double *ub, double *x, double *lam, uint32_t *active,
-                                             int32_t *status, int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_ref(const qpb_ref_desc *d, const double *P, const double *q,
-                                     const double *x0, double *x, int32_t *iters, hipStream_t stream);
-extern "C" hipError_t qpb_launch_qf_eval(int n, long long batch, const double *P, const double *q, double r,
-                                         const double *x, double *out, hipStream_t stream);
-extern "C" hipError_t qpb_launch_ref_invert(int n, long long batch, const double *P, double *Pinv,
-                                            hipStream_t stream);
-
-extern "C" hipError_t qpb_launch_ref_generate(int n, long long batch, unsigned long long first, unsigned seed,
-                                              const double *range, double *P, double *q, double *x0,
-                                              hipStream_t stream);
-extern "C" hipError_t qpb_launch_generate(int n, int m, long long batch, unsigned long long first,
-                                          unsigned long long seed, int family, double shift, double box, double *H,
-                                          double *f, double *A, double *b, hipStream_t stream);
+#include "qpb_launch.h"
+#include "qpb_route.h"
 
 static thread_local char g_err[512] = "";
 
@@ -90,15 +47,6 @@ static int check_device(void) {
   return 0;
 }
 
-// QPs per launch: a launch's grid holds at most 2^32 - 1 work-items, so each
-// kernel family takes at most 2^32 / (threads per QP) QPs per launch (minus a
-// margin); larger batches are split into consecutive launches on the stream.
-static long long chunk_qps(int n, int m, int flags = 0) {
-  if (n <= 16 && m <= 32 && !(flags & QPB_FLAG_DIAG_WAVE)) return 1LL << 27;  // 16 lanes per QP
-  if (n <= 32 && m <= 64) return 1LL << 25;  // 64 lanes per QP
-  return 1LL << 21;                          // n <= 128: one workgroup per CU walks the QPs (bounded chunks)
-}
-
 static int check_desc(const qpb_desc *d) {
   if (!d) return fail(QPB_ERR_INVALID_ARG, "desc is NULL");
   if (d->batch < 0) return fail(QPB_ERR_INVALID_ARG, "batch < 0");
@@ -107,6 +55,42 @@ static int check_desc(const qpb_desc *d) {
     return fail(QPB_ERR_UNSUPPORTED, "n=%d m=%d outside this build's kernels (n<=%d, m<=%d)", d->n, d->m,
                 QPB_MAX_N, QPB_MAX_M);
   return 0;
+}
+
+// The launcher of a kernel class, except gi_gram's (it takes the sections pointer too)
+static qpb_gi_launcher *launcher_of(qpb::Kernel k) {
+  switch (k) {
+    case qpb::Kernel::gi_dense: return qpb_launch_gi;
+    case qpb::Kernel::gi_wave: return qpb_launch_gi_wave;
+    case qpb::Kernel::gi_mixed: return qpb_launch_gi_mixed;
+    case qpb::Kernel::gi_box: return qpb_launch_gi_box;
+    case qpb::Kernel::gi_wave_box: return qpb_launch_gi_wave_box;
+    case qpb::Kernel::gi_gram_box: return qpb_launch_gi_gram_box;
+    case qpb::Kernel::gi_gram: break;
+  }
+  return nullptr;
+}
+
+// The batch in chunks of the route's step, one launch each (Ab, bb: A and b, or
+// lb and ub for the box kernels).  lam and active are NULL only at m = 0, iters
+// whenever the caller does not want it.
+static int solve_chunks(const qpb_desc *d, qpb::Route r, const double *H, const double *f,
+                        qpb::Batched<const double> Ab, qpb::Batched<const double> bb, double *x, double *lam,
+                        uint32_t *active, int32_t *status, int32_t *iters, hipStream_t stream, const char *what) {
+  const long long n = d->n, m = d->m;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const double *fc, const double *Ac, const double *bc, double *xc,
+          double *lc, uint32_t *ac, int32_t *sc, int32_t *ic) {
+        qpb_desc c = *d;
+        c.batch = count;
+        qpb_gi_launcher *const fn = launcher_of(r.kernel);
+        const hipError_t e = fn ? fn(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, stream)
+                                : qpb_launch_gi_gram(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, nullptr, stream);
+        return e == hipSuccess ? 0 : hip_fail(e, what);
+      },
+      qpb::required(H, n * n), qpb::required(f, n), Ab, bb, qpb::required(x, n), qpb::optional(lam, m),
+      qpb::optional(active, (m + 31) / 32), qpb::required(status, 1), qpb::optional(iters, 1));
 }
 
 extern "C" int qpb_solve(const qpb_desc *d, const double *H, const double *f, const double *A,
@@ -120,29 +104,8 @@ extern "C" int qpb_solve(const qpb_desc *d, const double *H, const double *f, co
     return fail(QPB_ERR_INVALID_ARG, "A, b, lam and active are required when m > 0");
   rc = check_device();
   if (rc) return rc;
-  // n <= 16, m <= 32: four QPs per wavefront; n <= 32, m <= 64: one QP per
-  // wavefront; larger: one QP per workgroup
-  const long long n = d->n, m = d->m, w = (m + 31) / 32, step = chunk_qps(d->n, d->m, d->flags);
-  for (long long k0 = 0; k0 < d->batch; k0 += step) {
-    qpb_desc c = *d;
-    c.batch = d->batch - k0 < step ? d->batch - k0 : step;
-    const double *Hc = H + k0 * n * n, *fc = f + k0 * n;
-    const double *Ac = m ? A + k0 * m * n : A, *bc = m ? b + k0 * m : b;
-    double *xc = x + k0 * n, *lc = m ? lam + k0 * m : lam;
-    uint32_t *ac = m ? active + k0 * w : active;
-    int32_t *sc = status + k0, *ic = iters ? iters + k0 : iters;
-    hipError_t e;
-    if (d->n <= 16 && d->m <= 32 && !(d->flags & QPB_FLAG_DIAG_WAVE))
-      e = qpb_launch_gi(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, (hipStream_t)stream);
-    else if (d->n > 16 && d->n <= 32 && d->m <= 64 && (d->flags & QPB_FLAG_MIXED))
-      e = qpb_launch_gi_mixed(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, (hipStream_t)stream);
-    else if (d->n <= 32 && d->m <= 64)
-      e = qpb_launch_gi_wave(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, (hipStream_t)stream);
-    else
-      e = qpb_launch_gi_gram(&c, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, nullptr, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "qpb_solve launch");
-  }
-  return 0;
+  return solve_chunks(d, qpb::route(d->n, d->m, d->flags, false), H, f, qpb::optional(A, (long long)d->m * d->n),
+                      qpb::optional(b, d->m), x, lam, active, status, iters, (hipStream_t)stream, "qpb_solve launch");
 }
 
 extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
@@ -156,20 +119,11 @@ extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f
     return fail(QPB_ERR_INVALID_ARG, "H, f, x, lam, active and status are required");
   rc = check_device();
   if (rc) return rc;
-  // n <= 16: four QPs per wavefront (qpb_gi_box.hip), at most 2^27 QPs per
-  // launch (2^32 work-items); 16 < n <= 32: one QP per wavefront (the BOX
-  // instantiation of qpb_gi_wave.hip), 2^25; 32 < n <= 128: one QP per
-  // workgroup (the BOX instantiation of qpb_gi_gram.hip, a persistent grid)
-  const long long n = d->n, w = (2 * n + 31) / 32, step = n <= 16 ? 1LL << 27 : 1LL << 25;
-  for (long long k0 = 0; k0 < d->batch; k0 += step) {
-    qpb_desc c = *d;
-    c.batch = d->batch - k0 < step ? d->batch - k0 : step;
-    hipError_t e = (n <= 16 ? qpb_launch_gi_box : n <= 32 ? qpb_launch_gi_wave_box : qpb_launch_gi_gram_box)(
-        &c, H + k0 * n * n, f + k0 * n, lb ? lb + k0 * n : lb, ub ? ub + k0 * n : ub, x + k0 * n, lam + k0 * 2 * n,
-        active + k0 * w, status + k0, iters ? iters + k0 : iters, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "qpb_solve_box launch");
-  }
-  return 0;
+  // n <= 16: qpb_gi_box.hip; 16 < n <= 32 and 32 < n <= 128: the BOX
+  // instantiations of qpb_gi_wave.hip and qpb_gi_gram.hip.  lb / ub may be NULL
+  return solve_chunks(d, qpb::route(d->n, d->m, d->flags, true), H, f, qpb::optional(lb, d->n),
+                      qpb::optional(ub, d->n), x, lam, active, status, iters, (hipStream_t)stream,
+                      "qpb_solve_box launch");
 }
 
 extern "C" int qpb_solve_sections(const qpb_desc *d, const double *H, const double *f, const double *A,
@@ -182,19 +136,18 @@ extern "C" int qpb_solve_sections(const qpb_desc *d, const double *H, const doub
   if (sections && sections_len < QPB_SECTIONS_LEN)
     return fail(QPB_ERR_INVALID_ARG, "sections: the buffer must hold QPB_SECTIONS_LEN (256 x 20) counters");
   if (d->batch == 0) return 0;
-  const bool n16 = d->n == 16 && d->m > 16 && d->m <= 32, wave = d->n > 16 && d->n <= 32 && d->m <= 64;
-  const bool gram = !(d->n <= 32 && d->m <= 64) && d->batch <= chunk_qps(d->n, d->m);
+  // the stamped builds exist per size class, whatever the flags; one launch
+  const qpb::Route r = qpb::route(d->n, d->m, 0, false);
+  const bool n16 = r.kernel == qpb::Kernel::gi_dense && d->n == 16 && d->m > 16;
+  const bool wave = r.kernel == qpb::Kernel::gi_wave && d->n > 16;
+  const bool gram = r.kernel == qpb::Kernel::gi_gram && d->batch <= r.step;
   if (!(n16 || wave || gram) || !sections)
     return fail(QPB_ERR_UNSUPPORTED, "sections: n=16 with 16<m<=32, 16<n<=32 with m<=64, or the n<=128 class");
   rc = check_device();
   if (rc) return rc;
-  hipError_t e;
-  if (n16)
-    e = qpb_launch_gi_sections(d, H, f, A, b, x, lam, active, status, iters, sections, (hipStream_t)stream);
-  else if (wave)
-    e = qpb_launch_gi_wave_sections(d, H, f, A, b, x, lam, active, status, iters, sections, (hipStream_t)stream);
-  else
-    e = qpb_launch_gi_gram(d, H, f, A, b, x, lam, active, status, iters, sections, (hipStream_t)stream);
+  qpb_gi_sections_launcher *const fn =
+      n16 ? qpb_launch_gi_sections : wave ? qpb_launch_gi_wave_sections : qpb_launch_gi_gram;
+  const hipError_t e = fn(d, H, f, A, b, x, lam, active, status, iters, sections, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "qpb_solve_sections launch");
   return 0;
 }
@@ -278,15 +231,17 @@ extern "C" int qpb_ref_solve(const qpb_ref_desc *d, const double *P, const doubl
   if (rc) return rc;
   // n <= 64: one 64-thread workgroup per QP, at most 2^25 QPs per launch
   // (n > 64: a grid of one workgroup per CU walks the batch)
-  const long long n = d->n, step = 1LL << 25;
-  for (long long k0 = 0; k0 < d->batch; k0 += step) {
-    qpb_ref_desc c = *d;
-    c.batch = d->batch - k0 < step ? d->batch - k0 : step;
-    hipError_t e = qpb_launch_ref(&c, P + k0 * n * n, q + k0 * n, x0 ? x0 + k0 * n : x0, x + k0 * n,
-                                  iters ? iters + k0 : iters, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "qpb_ref_solve launch");
-  }
-  return 0;
+  const long long n = d->n;
+  return qpb::for_each_chunk(
+      d->batch, 1LL << 25,
+      [&](long long count, const double *Pc, const double *qc, const double *x0c, double *xc, int32_t *ic) {
+        qpb_ref_desc c = *d;
+        c.batch = count;
+        const hipError_t e = qpb_launch_ref(&c, Pc, qc, x0c, xc, ic, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_ref_solve launch");
+      },
+      qpb::required(P, n * n), qpb::required(q, n), qpb::optional(x0, n), qpb::required(x, n),
+      qpb::optional(iters, 1));
 }
 
 extern "C" int qpb_ref_solve_host(const qpb_ref_desc *d, const double *P, const double *q, const double *x0,
@@ -319,13 +274,14 @@ extern "C" int qpb_matrix_invert(int32_t n, int64_t batch, const double *P, doub
   if (!P || !Pinv) return fail(QPB_ERR_INVALID_ARG, "P and Pinv are required");
   int rc = check_device();
   if (rc) return rc;
-  const long long nn = (long long)n * n, step = 1LL << 25;  // one 64-thread workgroup per matrix
-  for (long long k0 = 0; k0 < batch; k0 += step) {
-    const long long c = batch - k0 < step ? batch - k0 : step;
-    hipError_t e = qpb_launch_ref_invert(n, c, P + k0 * nn, Pinv + k0 * nn, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "qpb_matrix_invert launch");
-  }
-  return 0;
+  const long long nn = (long long)n * n;
+  return qpb::for_each_chunk(
+      batch, 1LL << 25,  // one 64-thread workgroup per matrix
+      [&](long long count, const double *Pc, double *Ic) {
+        const hipError_t e = qpb_launch_ref_invert(n, count, Pc, Ic, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_matrix_invert launch");
+      },
+      qpb::required(P, nn), qpb::required(Pinv, nn));
 }
 
 extern "C" int qpb_qf_eval(int32_t n, int64_t batch, const double *P, const double *q, double r, const double *x,

@@ -26,6 +26,11 @@ hipError_t qpb_with_workspace(hipStream_t stream, size_t bytes, const std::funct
 namespace qpb {
 
 constexpr double kInf = __builtin_huge_val();
+constexpr double kDepTol = 1e-24;  // |d2|^2 <= kDepTol |d|^2  <=>  z = 0: a dependent row, no direction
+// LDS bytes of a one-wave workgroup for 12 per CU, 3 per SIMD (11 from 13,056 B: tools/probe/occupancy_probe.hip)
+constexpr int kWaveLdsMax = 12800;
+constexpr int32_t kRedoStatus = 100;  // between two launches: gi_mixed marks the QPs gi_wave's REDO form re-solves
+__host__ __device__ constexpr int lrow(int i) { return i * (i + 1) / 2; }  // packed lower triangle: start of row i
 
 // compile-time unrolled loop: f(std::integral_constant<int, I>) for I = 0..N-1
 template <class F, int... I>
@@ -35,6 +40,28 @@ __device__ __forceinline__ void unroll_impl(F &&f, std::integer_sequence<int, I.
 template <int N, class F>
 __device__ __forceinline__ void unroll(F &&f) {
   unroll_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// sum_{j<N} x(j) y(j) with 2 independent accumulators
+template <int N, class FX, class FY>
+__device__ __forceinline__ double dot2(FX &&x, FY &&y, double init = 0.0) {
+  double a0 = init, a1 = 0.0;
+  unroll<N>([&](auto J) {
+    constexpr int j = J;
+    if constexpr (j % 2 == 0) a0 = __builtin_fma(x(j), y(j), a0);
+    else a1 = __builtin_fma(x(j), y(j), a1);
+  });
+  return a0 + a1;
+}
+
+// 16 doubles from LDS (16-byte aligned) as 8 b128 reads
+__device__ __forceinline__ void lds_row16(const double *src, double (&dst)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; j += 2) {
+    const double2 v = *reinterpret_cast<const double2 *>(&src[j]);
+    dst[j] = v.x;
+    dst[j + 1] = v.y;
+  }
 }
 
 // DPP controls (gfx9 encoding)
@@ -54,27 +81,6 @@ template <int N>
 __device__ __forceinline__ double ror(double v) {
   return __builtin_amdgcn_mov_dpp(v, kRowRor + N, 0xF, 0xF, true);
 }
-template <int N>
-__device__ __forceinline__ int rori(int v) {
-  return __builtin_amdgcn_mov_dpp(v, kRowRor + N, 0xF, 0xF, true);
-}
-
-// (value, index) min over the 16 lanes of the row; ties -> smaller index.
-// Exact (no rounding), so every lane ends with the identical pair.
-template <int N>
-__device__ __forceinline__ void argmin_step(double &v, int &i) {
-  const double v2 = ror<N>(v);
-  const int i2 = rori<N>(i);
-  const bool take = (v2 < v) || (v2 == v && i2 < i);
-  v = take ? v2 : v;
-  i = take ? i2 : i;
-}
-__device__ __forceinline__ void row_argmin(double &v, int &i) {
-  argmin_step<8>(v, i);
-  argmin_step<4>(v, i);
-  argmin_step<2>(v, i);
-  argmin_step<1>(v, i);
-}
 
 // Ordering point for LDS traffic between lanes of ONE wavefront.  A wave's DS
 // instructions execute in issue order, so only the compiler has to be kept
@@ -89,10 +95,6 @@ __device__ __forceinline__ void wave_lds_sync() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_wave_barrier();
 }
-
-}  // namespace qpb
-
-namespace qpb {
 
 // 1/x and 1/sqrt(x) from the hardware estimates (v_rcp_f64 / v_rsq_f64) plus
 // two Newton steps: full fp64 accuracy (<= 1 ulp), ~6 instructions instead of
@@ -126,17 +128,9 @@ __device__ __forceinline__ double rsq1(double x) {
 
 constexpr double kBig = 1.7976931348623157e308;  // DBL_MAX: the "no candidate" key
 
-// min-reduction key: a finite double whose low 5 mantissa bits carry an index
-// (value perturbed by <= 31 ulp).  v_min_f64 over the 16 lanes then yields the
-// minimum and its index together, 3 instructions per DPP step.
-__device__ __forceinline__ double pack_key(double v, int idx) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  return __builtin_bit_cast(double, (b & ~31ull) | (unsigned long long)idx);
-}
-__device__ __forceinline__ int key_index(double k) {
-  return (int)(__builtin_bit_cast(unsigned long long, k) & 31ull);
-}
-// the same with a 6-bit index (one QP per 64-lane wave)
+// min-reduction key: a finite double whose low 6 mantissa bits carry a lane
+// index (value perturbed by <= 63 ulp).  v_min_f64 over the lanes then yields
+// the minimum and its index together, 3 instructions per DPP step.
 __device__ __forceinline__ double pack_key64(double v, int idx) {
   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
   return __builtin_bit_cast(double, (b & ~63ull) | (unsigned long long)idx);
@@ -198,10 +192,7 @@ __device__ __forceinline__ void fmac_bc_nop(double &acc, double src, double mul)
                : "v"(src), "v"(mul), "i"(K));
 }
 
-// exact min over the 16 lanes of the row (v_min_f64 on row_ror moves)
-__device__ __forceinline__ double row_min_exact(double v) { return row_min(v); }
-
-// The same without the canonicalising v_max_f64 that fmin() adds behind every
+// row_min without the canonicalising v_max_f64 that fmin() adds behind every
 // DPP move (4 fp64 instructions per reduction).  Operands are finite or
 // +-inf (never NaN) wherever it is used.
 __device__ __forceinline__ double fmin_raw(double a, double b) {
@@ -230,6 +221,21 @@ __device__ __forceinline__ uint32_t row_min_u32(uint32_t v) {
   return v;
 }
 
+// ---- wave level: over the 4 rows of the 64-lane wavefront --------------------
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+  const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, lane);
+  const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
+  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+// exact min over the 64 lanes (wave-uniform result)
+__device__ __forceinline__ double wave_min(double v) {
+  v = row_min(v);
+  const double a = readlane_d(v, 0), b = readlane_d(v, 16), c = readlane_d(v, 32), d = readlane_d(v, 48);
+  return __builtin_fmin(__builtin_fmin(a, b), __builtin_fmin(c, d));
+}
+__device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0; }
+
 // max of a per-row-uniform int over the 4 rows of the wave, as a wave-uniform
 // (SGPR) value: bounds for skipping dead steps of unrolled loops.
 __device__ __forceinline__ int wave_max4(int v) {
@@ -237,12 +243,6 @@ __device__ __forceinline__ int wave_max4(int v) {
   const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
   const int ab = a > b ? a : b, cd = c > d ? c : d;
   return ab > cd ? ab : cd;
-}
-__device__ __forceinline__ int wave_min4(int v) {
-  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-  const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-  const int ab = a < b ? a : b, cd = c < d ? c : d;
-  return ab < cd ? ab : cd;
 }
 
 // Diagnostic builds only (STAMP = true, qpb_solve_sections): s_memrealtime stamps

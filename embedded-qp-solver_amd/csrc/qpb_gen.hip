@@ -23,7 +23,7 @@
 //    to the same QPs of the full batch; H = B^T B / (1e3 n) + shift I with
 //    the n x n product on the matrix cores (v_mfma_f64_16x16x4_f64).
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 namespace gen {

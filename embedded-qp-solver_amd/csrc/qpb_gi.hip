@@ -52,7 +52,7 @@
 // No branch or select compares the lane id with a compile-time constant:
 // such masks are hoisted by the compiler and end up spilled (SGPR pressure).
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 
@@ -60,10 +60,9 @@ constexpr int NL = 16;  // lanes per QP
 constexpr int QPB = 4;  // QPs per workgroup (one wavefront)
 constexpr int RS = 18;  // row stride (doubles) of the input transposes: conflict-free b128
 
-// packed lower triangle of L: row i at i(i+1)/2.  Reads may run past a row's
+// packed lower triangle of L (lrow).  Reads may run past a row's
 // end into the next rows (always inside the QP's slot): the solves never use
 // those values.
-__host__ __device__ constexpr int lrow(int i) { return i * (i + 1) / 2; }
 constexpr int L_SIZE = lrow(NL);  // 136
 
 // LDS slot of one QP: 394 doubles = 3,152 B, 12,608 B per wave -> 12 waves
@@ -78,33 +77,9 @@ constexpr int OFF_T = L_SIZE;             // R, column-major 16 x 16: R[i][j] at
                                           // the exchange row outside a DROP
 constexpr int OFF_XCH = OFF_T + NL * NL;  // 392: s_p, |d|^2 of the exchange
 constexpr int SLOT = OFF_XCH + 2;         // 394
-constexpr int kWaveLdsMax = 12800;        // bytes per one-wave workgroup for 12 per CU
-constexpr double kDepTol = 1e-24;         // |d2|^2 <= kDepTol |d|^2  <=>  z = 0
 static_assert(SLOT % 2 == 0 && OFF_T % 2 == 0 && OFF_XCH % 2 == 0, "b128 alignment");
 static_assert(4 * SLOT * 8 <= kWaveLdsMax, "12 waves (3 per SIMD) per CU by LDS");
 static_assert(NL * RS <= SLOT, "input transposes are staged over the whole slot");
-
-// sum_{j<N} x(j) y(j) with 2 independent accumulators
-template <int N, class FX, class FY>
-__device__ __forceinline__ double dot2(FX &&x, FY &&y, double init = 0.0) {
-  double a0 = init, a1 = 0.0;
-  unroll<N>([&](auto J) {
-    constexpr int j = J;
-    if constexpr (j % 2 == 0) a0 = __builtin_fma(x(j), y(j), a0);
-    if constexpr (j % 2 == 1) a1 = __builtin_fma(x(j), y(j), a1);
-  });
-  return a0 + a1;
-}
-
-// 16 doubles from LDS (16-byte aligned) as 8 b128 reads
-__device__ __forceinline__ void lds_row16(const double *src, double (&dst)[NL]) {
-#pragma unroll
-  for (int j = 0; j < NL; j += 2) {
-    const double2 v = *reinterpret_cast<const double2 *>(&src[j]);
-    dst[j] = v.x;
-    dst[j + 1] = v.y;
-  }
-}
 
 // out[r] = sum_j vec[lane j] * x[r][j] over the row's 16 lanes, DPP-fused;
 // the MR rows interleaved, two chains each (2 MR independent accumulators);
@@ -788,8 +763,7 @@ extern "C" hipError_t qpb_launch_gi(const qpb_desc *d, const double *H, const do
                                     const double *b, double *x, double *lam, uint32_t *active,
                                     int32_t *status, int32_t *iters, hipStream_t stream) {
   const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
 #define QPB_GI_LAUNCH(MR, N16, FULL)                                                                               \
   hipLaunchKernelGGL((qpb::gi_dense_kernel<MR, N16, FULL, false, 3>), dim3((unsigned)blocks), dim3(64), 0, stream, \
                      H, f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol,    \
@@ -814,8 +788,7 @@ extern "C" hipError_t qpb_launch_gi_sections(const qpb_desc *d, const double *H,
                                              int32_t *status, int32_t *iters, unsigned long long *sections,
                                              hipStream_t stream) {
   const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
   if (d->n != 16 || d->m <= 16) return hipErrorInvalidValue;
 #ifdef QPB_WAVE_TRACE
   // the diagnostic build launches the shipped kernel and writes 8 words per

@@ -21,7 +21,7 @@
 // 0..n-1, lower bounds n..2n-1), i.e. A = [I; -I] row order.  Infinite bounds
 // (or a NULL lb / ub) are absent constraints: their slack is +inf.
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 namespace box {
@@ -29,39 +29,17 @@ namespace box {
 constexpr int NL = 16;  // lanes per QP
 constexpr int QPB = 4;  // QPs per wavefront
 constexpr int RS = 18;  // row stride of the H transpose (conflict-free b128 rows)
-__host__ __device__ constexpr int lrow(int i) { return i * (i + 1) / 2; }
 constexpr int L_SIZE = lrow(NL);  // 136
 // per QP: L packed (136) | R column-major 16 x 16 with zero diagonal | exchange 32
 constexpr int OFF_L = 0;
 constexpr int OFF_R = L_SIZE;
 constexpr int OFF_XCH = OFF_R + NL * NL;
 constexpr int SLOT = OFF_XCH + 2;  // 394 doubles: s_p (the exchange row is R's column 0, as qpb_gi.hip)
-constexpr double kDepTol = 1e-24;
 static_assert(NL * RS <= SLOT, "the H transpose is staged over the whole slot");
 // 12 one-wave workgroups per CU need <= 12,800 B of LDS each (qpb_gi.hip,
 // tools/probe/occupancy_probe.hip); the round-4 slot (424 doubles = 13,568 B)
 // ran 11
-static_assert(4 * SLOT * 8 <= 12800, "12 waves per CU by LDS");
-
-template <int N, class FX, class FY>
-__device__ __forceinline__ double dot2(FX &&x, FY &&y) {
-  double a0 = 0.0, a1 = 0.0;
-  unroll<N>([&](auto J) {
-    constexpr int j = J;
-    if constexpr (j % 2 == 0) a0 = __builtin_fma(x(j), y(j), a0);
-    else a1 = __builtin_fma(x(j), y(j), a1);
-  });
-  return a0 + a1;
-}
-
-__device__ __forceinline__ void lds_row16(const double *src, double (&dst)[NL]) {
-#pragma unroll
-  for (int j = 0; j < NL; j += 2) {
-    const double2 v = *reinterpret_cast<const double2 *>(&src[j]);
-    dst[j] = v.x;
-    dst[j + 1] = v.y;
-  }
-}
+static_assert(4 * SLOT * 8 <= kWaveLdsMax, "12 waves per CU by LDS");
 
 // N16: n == 16 (coalesced H loads through an LDS transpose); otherwise the
 // rows are padded with the identity and the padded variables get no bounds
@@ -468,13 +446,9 @@ extern "C" hipError_t qpb_launch_gi_box(const qpb_desc *d, const double *H, cons
                                         const double *ub, double *x, double *lam, uint32_t *active, int32_t *status,
                                         int32_t *iters, hipStream_t stream) {
   const long long blocks = (d->batch + qpb::box::QPB - 1) / qpb::box::QPB;
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (3 * d->n) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
-  if (d->n == 16)
-    hipLaunchKernelGGL(qpb::box::gi_box_kernel<true>, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x,
-                       lam, active, status, iters, d->n, (long long)d->batch, max_iter, tol);
-  else
-    hipLaunchKernelGGL(qpb::box::gi_box_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x,
-                       lam, active, status, iters, d->n, (long long)d->batch, max_iter, tol);
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const auto kernel = d->n == 16 ? qpb::box::gi_box_kernel<true> : qpb::box::gi_box_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x, lam, active, status,
+                     iters, d->n, (long long)d->batch, max_iter, tol);
   return hipGetLastError();
 }

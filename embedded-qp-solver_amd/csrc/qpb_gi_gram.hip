@@ -41,7 +41,7 @@
 // columns in the loop), the diagonal-tile inverses (setup) / the rows of Q1
 // (loop; rows past QL live in a per-workgroup global scratch), vectors.
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 namespace gram {
@@ -86,11 +86,11 @@ static_assert(OFF_ROWS + 8 * LIT <= OFF_BUF, "diagonal-tile inverses fit the row
 constexpr int R_KEY = 0;    // per-wave selection keys (NWV)
 constexpr int R_T1 = 8;     // per-wave (ratio min, argmin position) pairs (2 NWV)
 constexpr int R_ND2 = 24;   // per-wave partial |w|^2 (NWV)
-constexpr double kDepTol = 1e-24;
 constexpr long long SCRATCH = LP + (long long)(NB - QL) * NB;  // doubles per workgroup
 
 using d4 = __attribute__((__vector_size__(4 * sizeof(double)))) double;
 
+// (not lrow(i) + j: the signed division compiles to other code than the shift)
 __device__ __forceinline__ int tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }
 // column c -> its place in the permuted vector layout (lane group c & 3 reads
 // a contiguous 32-double block in the order of its registers)
@@ -101,23 +101,11 @@ __device__ __forceinline__ double mfma(double a, double b, d4 &c) {
   c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
   return 0.0;
 }
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
 __device__ __forceinline__ double pack_key256(double v, int idx) {
   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
   return __builtin_bit_cast(double, (b & ~255ull) | (unsigned long long)idx);
 }
 __device__ __forceinline__ int key_index256(double k) { return (int)(__builtin_bit_cast(unsigned long long, k) & 255ull); }
-// min over the 64 lanes of a wave (exact), on every lane
-__device__ __forceinline__ double wave_min(double v) {
-  v = row_min(v);
-  return __builtin_fmin(__builtin_fmin(readlane_d(v, 0), readlane_d(v, 16)),
-                        __builtin_fmin(readlane_d(v, 32), readlane_d(v, 48)));
-}
 __device__ __forceinline__ double wave_sum(double v) {
   v = row_sum(v);
   return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
@@ -472,6 +460,8 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
     const long long g = flags[1];
     if (g >= batch) break;
     const double *Hq = Hg + g * (long long)n * n;
+    // BOX: A is implicit and Ag holds lb (n per QP, maybe NULL), so no A row exists to point at; Aq aliases
+    // Hq only to stay a valid pointer and is never read there (its one read is in the !BOX branch of the setup)
     const double *Aq = BOX ? Hq : Ag + g * (long long)m * n;
 
     // ------------------------------------------------------------ setup
@@ -1047,8 +1037,7 @@ template <bool BOX>
 static hipError_t launch_gi_gram(const qpb_desc *d, const double *H, const double *f, const double *A,
                                  const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
                                  int32_t *iters, unsigned long long *sections, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
   int dev = 0, cus = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;

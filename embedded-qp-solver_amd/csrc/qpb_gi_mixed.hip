@@ -34,7 +34,7 @@
 #include <type_traits>
 
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 namespace mx {
@@ -52,7 +52,6 @@ static_assert(OFF_D % 4 == 0, "fp64 area 16-byte aligned");
 constexpr float kDepTol32 = 1e-10f;  // |d2|^2 <= kDepTol32 |d|^2  <=>  z = 0 (fp32 noise ~1e-14)
 constexpr float kFeas32 = 1e-6f;     // fp32 violation threshold (relative); fp64 verifies against feas_tol
 constexpr int kRefine = 3;           // fp64 refinement steps (at most; stops once converged)
-constexpr int32_t kRedo = 100;       // internal status: re-solve in fp64
 #ifndef QPB_MX_OCC
 #define QPB_MX_OCC 3  // waves per SIMD
 #endif
@@ -62,12 +61,6 @@ constexpr int32_t kRedo = 100;       // internal status: re-solve in fp64
 
 __device__ __forceinline__ float readlane_f(float v, int lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 template <int CTRL>
 __device__ __forceinline__ float dppf(float v) {
@@ -98,7 +91,6 @@ __device__ __forceinline__ double wave_maxd(double v) {
   const double a = readlane_d(v, 0), b = readlane_d(v, 16), c = readlane_d(v, 32), d = readlane_d(v, 48);
   return __builtin_fmax(__builtin_fmax(a, b), __builtin_fmax(c, d));
 }
-__device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0; }
 __device__ __forceinline__ void pinf(float &v) { asm volatile("" : "+v"(v)); }
 // a finite fp32 key whose low 6 mantissa bits carry a lane index
 __device__ __forceinline__ float pack_key64f(float v, int idx) {
@@ -139,8 +131,6 @@ __device__ __forceinline__ double row_dot(const double *__restrict__ row, int n,
   }
   return a0 + a1;
 }
-
-__host__ __device__ constexpr int lrow(int i) { return i * (i + 1) / 2; }
 
 // (R^T R)^{-1} c over the q active positions (position j in lane j), fp64
 // arithmetic with the fp32 R (column-major, zero diagonal) and its diagonal
@@ -719,7 +709,7 @@ __global__ __launch_bounds__(64, OCC) void gi_mixed_kernel(
       actg[g * words] = (uint32_t)bal;
       if (words > 1) actg[g * words + 1] = (uint32_t)(bal >> 32);
     }
-    statg[g] = redo ? kRedo : QPB_OK;
+    statg[g] = redo ? kRedoStatus : QPB_OK;
     if (itg) itg[g] = it;
   }
 }
@@ -727,16 +717,10 @@ __global__ __launch_bounds__(64, OCC) void gi_mixed_kernel(
 }  // namespace mx
 }  // namespace qpb
 
-// the fp64 kernel over the QPs the mixed kernel marked (qpb_gi_wave.hip)
-extern "C" hipError_t qpb_launch_gi_wave_redo(const qpb_desc *d, const double *H, const double *f, const double *A,
-                                              const double *b, double *x, double *lam, uint32_t *active,
-                                              int32_t *status, int32_t *iters, hipStream_t stream);
-
 extern "C" hipError_t qpb_launch_gi_mixed(const qpb_desc *d, const double *H, const double *f, const double *A,
                                           const double *b, double *x, double *lam, uint32_t *active,
                                           int32_t *status, int32_t *iters, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
   hipLaunchKernelGGL(qpb::mx::gi_mixed_kernel<QPB_MX_OCC>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, b, x, lam,
                      active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol);
   hipError_t e = hipGetLastError();

@@ -42,9 +42,7 @@
 #include <type_traits>
 
 #include "qpb_common.h"
-#include "qpb.h"
-
-
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 namespace wv {
@@ -62,37 +60,8 @@ constexpr int SLOT = OFF_X + 2;                     // 1586 doubles = 12,688 B
 // a CU holds 12 one-wave workgroups of <= 12,800 B of LDS (11 from 13,056 B:
 // tools/probe/occupancy_probe.hip); the round-4 slot (RS = 34, a separate
 // exchange row: 13,248 B) ran 11
-static_assert(SLOT * 8 <= 12800, "12 waves (3 per SIMD) per CU by LDS");
+static_assert(SLOT * 8 <= kWaveLdsMax, "12 waves (3 per SIMD) per CU by LDS");
 static_assert(OFF_R % 2 == 0 && OFF_X % 2 == 0, "b128 alignment of the exchange row and s_p");
-constexpr double kDepTol = 1e-24;
-
-__host__ __device__ constexpr int lrow(int i) { return i * (i + 1) / 2; }
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(unsigned)b, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-// exact min over the 64 lanes (wave-uniform result)
-__device__ __forceinline__ double wave_min(double v) {
-  v = row_min(v);
-  const double a = readlane_d(v, 0), b = readlane_d(v, 16), c = readlane_d(v, 32), d = readlane_d(v, 48);
-  return __builtin_fmin(__builtin_fmin(a, b), __builtin_fmin(c, d));
-}
-__device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0; }
-
-template <int N, class FX, class FY>
-__device__ __forceinline__ double dot2(FX &&x, FY &&y, double init = 0.0) {
-  double a0 = init, a1 = 0.0;
-  unroll<N>([&](auto J) {
-    constexpr int j = J;
-    if constexpr (j % 2 == 0) a0 = __builtin_fma(x(j), y(j), a0);
-    else a1 = __builtin_fma(x(j), y(j), a1);
-  });
-  return a0 + a1;
-}
-
 // D[l,:] . v for a vector held as v[j] = vA at lane j (j < 16) and vB at
 // lane j - 16 (j >= 16) of every 16-lane row: the FMA takes v[j] by its own
 // DPP broadcast (row_newbcast), four accumulators.  The caller has issued
@@ -111,7 +80,6 @@ __device__ __forceinline__ void dpp_ready2(double a, double b) { asm volatile("s
 // one QP per wavefront; MR = 1 (m <= 64); OCC waves per SIMD
 // REDO: solve only the QPs the mixed-precision kernel marked (status
 // kRedoStatus, qpb_gi_mixed.hip); every other wave exits at once
-constexpr int32_t kRedoStatus = 100;
 template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
@@ -653,6 +621,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // masks live in SGPRs and spilled them (round 6: 112 SGPR spills).
   double *xcap = R + 2 * NP;
   double xl;
+  static_assert(lrow(NP - 1) + NP - 1 < L_SIZE, "the unmasked L reads below stay inside L: ll < NP must hold");
   {
     double Lrow[NP];  // row ll of L (entries past the diagonal: dead)
     unroll<NP>([&](auto K) {
@@ -718,48 +687,44 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
 }  // namespace wv
 }  // namespace qpb
 
+// one QP per 64-thread workgroup; the template arguments are the kernel's
+template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false>
+static hipError_t launch_gi_wave(const qpb_desc *d, const double *H, const double *f, const double *A,
+                                 const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                                 int32_t *iters, hipStream_t stream, unsigned long long *sections = nullptr) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<OCC, STAMP, REDO, BOX>), dim3((unsigned)d->batch), dim3(64), 0, stream,
+                     H, f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol,
+                     sections);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t qpb_launch_gi_wave(const qpb_desc *d, const double *H, const double *f, const double *A,
                                          const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
                                          int32_t *iters, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
   // three waves per SIMD: the 168-VGPR cap spills ~50 dwords, nearly all in
   // the setup sweep; measured 6.30 ms against 6.47 ms for two waves with the
   // same code at B = 262,144 (profiles/r02/ab_n32.json; round 1 measured
   // the opposite on its kernel)
-  hipLaunchKernelGGL(qpb::wv::gi_wave_kernel<3>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, b, x, lam,
-                     active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol);
-  return hipGetLastError();
+  return launch_gi_wave<3>(d, H, f, A, b, x, lam, active, status, iters, stream);
 }
 
 extern "C" hipError_t qpb_launch_gi_wave_sections(const qpb_desc *d, const double *H, const double *f,
                                                   const double *A, const double *b, double *x, double *lam,
                                                   uint32_t *active, int32_t *status, int32_t *iters,
                                                   unsigned long long *sections, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
-  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<2, true>), dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, b,
-                     x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol, sections);
-  return hipGetLastError();
+  return launch_gi_wave<2, true>(d, H, f, A, b, x, lam, active, status, iters, stream, sections);
 }
 
 extern "C" hipError_t qpb_launch_gi_wave_redo(const qpb_desc *d, const double *H, const double *f, const double *A,
                                               const double *b, double *x, double *lam, uint32_t *active,
                                               int32_t *status, int32_t *iters, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
-  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<2, false, true>), dim3((unsigned)d->batch), dim3(64), 0, stream, H, f,
-                     A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol);
-  return hipGetLastError();
+  return launch_gi_wave<2, false, true>(d, H, f, A, b, x, lam, active, status, iters, stream);
 }
 
 // qpb_solve_box for 16 < n <= 32 (m = 2n): A = [I; -I], b = [ub; -lb] implicit
 extern "C" hipError_t qpb_launch_gi_wave_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
                                              const double *ub, double *x, double *lam, uint32_t *active,
                                              int32_t *status, int32_t *iters, hipStream_t stream) {
-  const int max_iter = d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8;
-  const double tol = d->feas_tol > 0 ? d->feas_tol : 1e-10;
-  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, true>), dim3((unsigned)d->batch), dim3(64), 0, stream,
-                     H, f, lb, ub, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol);
-  return hipGetLastError();
+  return launch_gi_wave<3, false, false, true>(d, H, f, lb, ub, x, lam, active, status, iters, stream);
 }

@@ -1,0 +1,63 @@
+// qpb_launch.h -- the kernel launchers behind the C-ABI: the only place one is
+// declared.  Every file that defines or calls a launcher includes this header,
+// so the compiler checks each definition against its declaration.  The
+// launchers take a hipStream_t and check nothing; they are internal to
+// libqpb.so (hidden visibility), qpb_api.hip validates before it calls them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "qpb.h"
+
+#define QPB_LAUNCHER __attribute__((visibility("hidden")))
+
+extern "C" {
+// ---- the active-set solvers: one launch over d->batch QPs -------------------
+// The box forms (d->m == 2 d->n) take lb and ub, either may be NULL, where the
+// others take A and b.
+typedef hipError_t qpb_gi_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
+                                   const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                                   int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_launcher qpb_launch_gi,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave,                      // n <= 32, m <= 64 (qpb_gi_wave.hip)
+    qpb_launch_gi_wave_redo,                 // ... only the QPs whose status is qpb::kRedoStatus
+    qpb_launch_gi_mixed,                     // 16 < n <= 32: fp32, fp64 refinement, the redo launch (qpb_gi_mixed.hip)
+    qpb_launch_gi_box,                       // lb <= x <= ub, n <= 16 (qpb_gi_box.hip)
+    qpb_launch_gi_wave_box,                  // ... n <= 32 (qpb_gi_wave.hip)
+    qpb_launch_gi_gram_box;                  // ... n <= 128 (qpb_gi_gram.hip)
+// with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
+typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
+                                            const double *b, double *x, double *lam, uint32_t *active,
+                                            int32_t *status, int32_t *iters, unsigned long long *sections,
+                                            hipStream_t stream);
+QPB_LAUNCHER qpb_gi_sections_launcher qpb_launch_gi_sections,  // n = 16, 16 < m <= 32
+    qpb_launch_gi_wave_sections,                               // 16 < n <= 32, m <= 64
+    qpb_launch_gi_gram;  // n <= 128, m <= 256 (qpb_gi_gram.hip); sections NULL: the shipped kernel
+
+// ---- the reference-semantics kernels (qpb_ref.hip) --------------------------
+QPB_LAUNCHER hipError_t qpb_launch_ref(const qpb_ref_desc *d, const double *P, const double *q, const double *x0,
+                                       double *x, int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER hipError_t qpb_launch_qf_eval(int n, long long batch, const double *P, const double *q, double r,
+                                           const double *x, double *out, hipStream_t stream);
+QPB_LAUNCHER hipError_t qpb_launch_ref_invert(int n, long long batch, const double *P, double *Pinv,
+                                              hipStream_t stream);
+
+// ---- the problem generators (qpb_gen.hip) -----------------------------------
+QPB_LAUNCHER hipError_t qpb_launch_ref_generate(int n, long long batch, unsigned long long first, unsigned seed,
+                                                const double *range, double *P, double *q, double *x0,
+                                                hipStream_t stream);
+QPB_LAUNCHER hipError_t qpb_launch_generate(int n, int m, long long batch, unsigned long long first,
+                                            unsigned long long seed, int family, double shift, double box, double *H,
+                                            double *f, double *A, double *b, hipStream_t stream);
+}  // extern "C"
+
+// The limits a launcher hands its kernel: the descriptor's, or the defaults
+// where it leaves them at 0.  The box form has m = 2n.
+struct qpb_limits {
+  int max_iter;
+  double feas_tol;
+};
+static inline qpb_limits qpb_resolve_limits(const qpb_desc *d) {
+  return {d->max_iter > 0 ? d->max_iter : 4 * (d->n + d->m) + 8, d->feas_tol > 0 ? d->feas_tol : 1e-10};
+}

@@ -44,7 +44,7 @@
 // The arithmetic is the same code in the same order in every layout: only the
 // addresses, and the grouping of loads ahead of the stores, change.
 #include "qpb_common.h"
-#include "qpb.h"
+#include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
 
@@ -142,13 +142,6 @@ __device__ __forceinline__ double seq_norm(const double *a, int n) {
     acc += t;
   }
   return __builtin_sqrt(acc);
-}
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
 // matrix_lup_decompose (matrix_ops.c:487-536) in place on M, the permutation

@@ -123,6 +123,15 @@ def _stream_ptr(stream):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _empty_solution(B: int, n: int, m: int, dev) -> Solution:
+    import torch
+    return Solution(torch.empty((B, n), dtype=torch.float64, device=dev),
+                    torch.empty((B, m), dtype=torch.float64, device=dev),
+                    torch.empty((B, (m + 31) // 32), dtype=torch.int32, device=dev),
+                    torch.empty((B,), dtype=torch.int32, device=dev),
+                    torch.empty((B,), dtype=torch.int32, device=dev))
+
+
 def solve(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0, out: Solution | None = None,
           stream=None, flags: int = 0) -> Solution:
     """Batched min 1/2 x^T H x + f^T x s.t. A x <= b on the GPU (torch CUDA float64 tensors).
@@ -143,14 +152,8 @@ def solve(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0, out
             raise ValueError("inputs must be contiguous float64")
     if H.shape != (B, n, n) or (m and (A.shape != (B, m, n) or b.shape != (B, m))):
         raise ValueError("shape mismatch")
-    dev = f.device
-    w = (m + 31) // 32
     if out is None:
-        out = Solution(torch.empty((B, n), dtype=torch.float64, device=dev),
-                       torch.empty((B, m), dtype=torch.float64, device=dev),
-                       torch.empty((B, w), dtype=torch.int32, device=dev),
-                       torch.empty((B,), dtype=torch.int32, device=dev),
-                       torch.empty((B,), dtype=torch.int32, device=dev))
+        out = _empty_solution(B, n, m, f.device)
     d = Desc(n, m, B, max_iter, flags, feas_tol)
     rc = _lib.qpb_solve(ctypes.byref(d), _ptr(H), _ptr(f), _ptr(A) if m else None, _ptr(b) if m else None,
                         _ptr(out.x), _ptr(out.lam), _ptr(out.active), _ptr(out.status), _ptr(out.iters),
@@ -180,14 +183,9 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.
             raise ValueError("H, f, lb and ub must live on the same CUDA device")
     if H.shape != (B, n, n) or any(t is not None and t.shape != (B, n) for t in (lb, ub)):
         raise ValueError("shape mismatch")
-    dev = f.device
     m = 2 * n
     if out is None:
-        out = Solution(torch.empty((B, n), dtype=torch.float64, device=dev),
-                       torch.empty((B, m), dtype=torch.float64, device=dev),
-                       torch.empty((B, (m + 31) // 32), dtype=torch.int32, device=dev),
-                       torch.empty((B,), dtype=torch.int32, device=dev),
-                       torch.empty((B,), dtype=torch.int32, device=dev))
+        out = _empty_solution(B, n, m, f.device)
     d = Desc(n, m, B, max_iter, 0, feas_tol)
     rc = _lib.qpb_solve_box(ctypes.byref(d), _ptr(H), _ptr(f), _ptr(lb), _ptr(ub), _ptr(out.x), _ptr(out.lam),
                             _ptr(out.active), _ptr(out.status), _ptr(out.iters), _stream_ptr(stream))
