@@ -57,6 +57,16 @@ static int check_desc(const qpb_desc *d) {
   return 0;
 }
 
+// The arrays a dense solve reads and writes (qpb_solve, qpb_solve_sections);
+// iters may be NULL
+static int check_solve_arrays(const qpb_desc *d, const double *H, const double *f, const double *A, const double *b,
+                              const double *x, const double *lam, const uint32_t *active, const int32_t *status) {
+  if (!H || !f || !x || !status) return fail(QPB_ERR_INVALID_ARG, "H, f, x and status are required");
+  if (d->m > 0 && (!A || !b || !lam || !active))
+    return fail(QPB_ERR_INVALID_ARG, "A, b, lam and active are required when m > 0");
+  return 0;
+}
+
 // The launcher of a kernel class, except gi_gram's (it takes the sections pointer too)
 static qpb_gi_launcher *launcher_of(qpb::Kernel k) {
   switch (k) {
@@ -99,9 +109,8 @@ extern "C" int qpb_solve(const qpb_desc *d, const double *H, const double *f, co
   int rc = check_desc(d);
   if (rc) return rc;
   if (d->batch == 0) return 0;
-  if (!H || !f || !x || !status) return fail(QPB_ERR_INVALID_ARG, "H, f, x and status are required");
-  if (d->m > 0 && (!A || !b || !lam || !active))
-    return fail(QPB_ERR_INVALID_ARG, "A, b, lam and active are required when m > 0");
+  rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);
+  if (rc) return rc;
   rc = check_device();
   if (rc) return rc;
   return solve_chunks(d, qpb::route(d->n, d->m, d->flags, false), H, f, qpb::optional(A, (long long)d->m * d->n),
@@ -136,6 +145,8 @@ extern "C" int qpb_solve_sections(const qpb_desc *d, const double *H, const doub
   if (sections && sections_len < QPB_SECTIONS_LEN)
     return fail(QPB_ERR_INVALID_ARG, "sections: the buffer must hold QPB_SECTIONS_LEN (256 x 20) counters");
   if (d->batch == 0) return 0;
+  rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);
+  if (rc) return rc;
   // the stamped builds exist per size class, whatever the flags; one launch
   const qpb::Route r = qpb::route(d->n, d->m, 0, false);
   const bool n16 = r.kernel == qpb::Kernel::gi_dense && d->n == 16 && d->m > 16;

@@ -331,10 +331,12 @@ WAVE_SECTION_NAMES = ["load", "sweep", "init", "select", "exchange", "back_solve
 
 
 def solve_sections(H, f, A, b, sections, *, max_iter: int = 0, out: Solution | None = None, stream=None):
-    """Diagnostic builds of the n=16 (16<m<=32) and 16<n<=32 (m<=64) kernels:
-    accumulate per-section wave ticks (100 MHz) into the int64 CUDA tensor
-    ``sections`` (N_SECTIONS = 20 int64 entries; the first 12 are named by
-    SECTION_NAMES / WAVE_SECTION_NAMES)."""
+    """Diagnostic builds of the n=16 (16<m<=32), 16<n<=32 (m<=64) and Gram
+    (32<n<=128 or m>64, up to m=256; one launch, so a batch within the route's
+    step) kernels: accumulate per-section wave ticks (100 MHz) into the int64
+    CUDA tensor ``sections`` (N_SECTIONS = 20 int64 entries; the first 12 are
+    named by SECTION_NAMES / WAVE_SECTION_NAMES for the first two builds; the
+    Gram build stamps the first workgroup wave's ticks into 19 of them)."""
     import torch
     if not (sections.is_cuda and sections.dtype == torch.int64 and sections.is_contiguous()
             and sections.numel() >= N_SECTIONS):

@@ -114,8 +114,10 @@ typedef enum qpb_error {
 	QPB_ERR_NO_DEVICE = -4
 } qpb_error;
 
-/* diagnostic flag: every QP k reads the inputs of QP (k mod 512) -- kernel
- * time without HBM latency (outputs are still written for every k) */
+/* diagnostic flag (n <= 16, m <= 32, without QPB_FLAG_DIAG_WAVE): every QP k
+ * reads the inputs of QP (k mod 512) -- kernel time without HBM latency
+ * (outputs are still written for every k).  Ignored outside that size class
+ * and by qpb_solve_box. */
 #define QPB_FLAG_DIAG_L2 1
 /* flag values 4 and 8 (round-2 diagnostic builds of the n <= 16 kernel) are
  * retired: accepted and ignored */
@@ -220,8 +222,10 @@ int qpb_matrix_invert(int32_t n, int64_t batch, const double *P, double *Pinv,
 int qpb_qf_eval(int32_t n, int64_t batch, const double *P, const double *q,
 		double r, const double *x, double *out, void *stream);
 
-/* Diagnostic: same solve (n = 16 with 16 < m <= 32, or 16 < n <= 32 with
- * m <= 64) by a build of the kernel with s_memrealtime stamps (100 MHz); adds
+/* Diagnostic: same solve (n = 16 with 16 < m <= 32, 16 < n <= 32 with
+ * m <= 64, or the n <= 128 Gram class in one launch; QPB_ERR_UNSUPPORTED
+ * otherwise, and for sections == NULL; array pointers checked as by
+ * qpb_solve) by a build of the kernel with s_memrealtime stamps (100 MHz); adds
  * each wavefront's ticks per kernel section into row (workgroup index mod 256)
  * of sections[256][20] (zero it first; sum the rows for the totals).
  * sections_len is the device buffer's length in elements: below

@@ -110,6 +110,25 @@ def test_box_argument_errors_without_gpu():
         assert lib.qpb_solve_box(ctypes.byref(d), p, p, None, None, p, p, p, p, None, None) == -4
 
 
+def test_sections_argument_errors_without_gpu():
+    """qpb_solve_sections checks its array pointers as qpb_solve does, before any device work."""
+    lib = ctypes.CDLL(LIB)
+    vp = ctypes.c_void_p
+    lib.qpb_solve_sections.argtypes = [ctypes.POINTER(Desc)] + [vp] * 10 + [ctypes.c_int64, vp]
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, vp)
+    for n, m in ((16, 32), (20, 33), (48, 96)):  # the three stamped builds
+        d = Desc(n, m, 4, 0, 0, 0.0)
+        for null in (0, 1, 2, 3, 4, 5, 6, 7):  # H, f, A, b, x, lam, active, status; iters may be NULL
+            args = [p] * 10
+            args[null] = None
+            assert lib.qpb_solve_sections(ctypes.byref(d), *args, 256 * 20, None) == -1, (n, m, null)
+        assert lib.qpb_solve_sections(ctypes.byref(d), *([p] * 10), 256 * 20 - 1, None) == -1
+        assert lib.qpb_solve_sections(ctypes.byref(d), *([p] * 9), None, 256 * 20, None) == -2  # no counters
+    d = Desc(16, 32, 0, 0, 0, 0.0)
+    assert lib.qpb_solve_sections(ctypes.byref(d), *([None] * 10), 256 * 20, None) == 0  # batch 0
+
+
 def _device_present():
     # under the sanitizer run torch stays out of the process (it is not
     # instrumented and only answers this question); that run is CPU-only
