@@ -433,24 +433,33 @@ __device__ __forceinline__ void gi_group(
       // before: fmac_bc_nop issues the DPP read hazard's wait states)
       const double ninv = -invRd;
       double nacc = (l < q) ? Dpl : 0.0;  // = -d1_l
-      unroll<NL>([&](auto JJ) {
-        constexpr int j = NL - 1 - JJ;
-        // (column 0 holds no entry above the diagonal: skipped)
-        if (j > 0 && j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, Tv[j * NL + l]);
-      });
+      // steps 15 .. 1 in that order (column 0 holds no entry above the
+      // diagonal: skipped), each behind its wave-uniform test j < qmax.  The
+      // tests are grouped 15..8, 7..4, 3..1 under one test per group: a flat
+      // chain walked 12 to 14 failing tests per trip at the usual qmax of 2 or
+      // 3 (one scalar compare and branch each), the groups walk 1 + 3.
+      auto step = [&](auto JC) {
+        constexpr int j = JC;
+        if (j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, Tv[j * NL + l]);
+      };
+      if (qmax > 4) {
+        if (qmax > 8) unroll<8>([&](auto JJ) { step(std::integral_constant<int, NL - 1 - JJ>{}); });
+        unroll<4>([&](auto JJ) { step(std::integral_constant<int, 7 - JJ>{}); });
+      }
+      unroll<3>([&](auto JJ) { step(std::integral_constant<int, 3 - JJ>{}); });
       rm = nacc * ninv;  // r_l (0 for l >= q)
     }
     clk.tick(6);
 
     // ---- step lengths
     double t1 = kBig;
-    int k = 0;
+    bool attains = false;  // this position attains the minimum ratio (read by a DROP only)
     if (qmax > 0) {
-      // the exact minimum ratio, then the lowest position attaining it
+      // the exact minimum ratio; a DROP then takes the lowest position attaining it
       const double ratio = um * rcp1(rm);
       const bool cand = l < q && rm > 0.0;
       t1 = row_min_raw(cand ? ratio : kBig);
-      k = (int)row_min_u32(cand && ratio == t1 ? (uint32_t)l : 31u) & (NL - 1);
+      attains = cand && ratio == t1;
     }
     const double ir = rsq1(nd2);  // 1/|d2| (only used when nd2 > 0)
     const double t2 = (nd2 > kDepTol * dd) ? -sp * (ir * ir) : kBig;
@@ -522,7 +531,9 @@ __device__ __forceinline__ void gi_group(
       selecting = true;
       clk.tick(8);
     } else {
-      // ---------------- DROP active position k
+      // ---------------- DROP active position k, the lowest one attaining t1
+      // (the argmin is paid here, not on every trip: ADDs never read it)
+      const int k = (int)row_min_u32(attains ? (uint32_t)l : 31u) & (NL - 1);
       const int c = __shfl(iam, k, NL);
 #pragma unroll
       for (int r = 0; r < MR; ++r) act[r] = act[r] && !(l == (c & (NL - 1)) && r == (c >> 4));
@@ -626,9 +637,15 @@ __device__ __forceinline__ void gi_group(
   // with its own wait); the work that does not need them -- the multipliers by
   // row and their stores, the active-set word, L's row -- runs while they are
   // in flight.  Positions past qm read a valid row and are not summed.
-  const int ias = iam > 0 ? iam : 0;
-  asm volatile("s_nop 1" ::"v"(ias));  // its DPP reads below may sit behind a branch only
+  // Addresses: the byte offset of the position's row (m <= 32 rows of n <= 16
+  // doubles: below 4 KiB) is formed once per lane, before the broadcast, and
+  // each load adds the broadcast offset to this lane's column base -- a DPP
+  // move and one 64-bit add per load instead of a multiply, a sign extension
+  // and a shifted add behind every broadcast.
+  const uint32_t iob = (uint32_t)(iam > 0 ? iam : 0) * (uint32_t)n * 8u;
+  asm volatile("s_nop 1" ::"v"(iob));  // its DPP reads below may sit behind a branch only
   const int lc = l < n ? l : n - 1;
+  const char *Acol = reinterpret_cast<const char *>(Aqo + lc);
   double arow[NL];
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
@@ -636,7 +653,7 @@ __device__ __forceinline__ void gi_group(
       __builtin_amdgcn_sched_barrier(0);
       unroll<8>([&](auto K) {
         constexpr int kk = k0 + K;
-        arow[kk] = Aqo[bci<kk>(ias) * n + lc];
+        arow[kk] = *reinterpret_cast<const double *>(Acol + (uint32_t)bci<kk>((int)iob));
       });
     }
   });

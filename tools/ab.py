@@ -2,6 +2,8 @@
 """A/B timing of libqpb variants (tools/build_variant.sh) on the same batch,
 rounds interleaved so clock/thermal drift hits every variant alike.
   python tools/ab.py name1 name2 ...   ('head' = lib/libqpb.so; name@flags adds qpb_desc.flags)
+Per variant: the median and minimum over all launches, the median of each round and their
+spread (max - min), the noise a difference between two variants has to clear.
 env: B (1048576), FAM (box), ROUNDS (5), REPS (6), MAXIT (0 = the default cap; 1 = setup + one trip),
      BOXAPI (1: time qpb_solve_box on the same QPs, lb = -b[n:], ub = b[:n])"""
 import ctypes
@@ -47,6 +49,7 @@ def main(names):
         assert rc == 0, rc
 
     times = {nm: [] for nm in names}
+    rmed = {nm: [] for nm in names}  # the median of each round: their max - min is the variant's spread
     for nm in names:
         for _ in range(3):
             call(nm)
@@ -59,6 +62,7 @@ def main(names):
                 e1.record(s)
                 e1.synchronize()
                 times[nm].append(e0.elapsed_time(e1) * 1e3)
+            rmed[nm].append(sorted(times[nm][-reps:])[reps // 2])
     torch.cuda.synchronize()
     ref = names[0]
     out = {}
@@ -66,6 +70,8 @@ def main(names):
         t = sorted(times[nm])
         same = bool(torch.equal(sols[nm].x, sols[ref].x) and torch.equal(sols[nm].active, sols[ref].active))
         out[nm or "head"] = {"median_us": round(t[len(t) // 2], 1), "min_us": round(t[0], 1),
+                             "round_medians_us": [round(x, 1) for x in rmed[nm]],
+                             "spread_us": round(max(rmed[nm]) - min(rmed[nm]), 1),
                              "same_as_first": same, "iters_mean": float(sols[nm].iters.double().mean())}
     print(json.dumps({"B": B, "family": fam, "max_iter": maxit, "api": "qpb_solve_box" if boxapi else "qpb_solve",
                       "variants": out}, indent=1))

@@ -6,7 +6,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import oracle
 
 def gi(H, f, A, b, rule, tol=1e-10, trace=None):
-    # trace: a list that receives (q, 'add' | 'drop') per iteration when given
+    # trace: a list that receives (q, 'add' | 'drop', k) per iteration when given
+    # (k: the active position a drop removes, -1 for an add)
     n = len(f); m = len(b)
     L = np.linalg.cholesky(H)
     D0 = np.linalg.solve(L, A.T).T          # A L^{-T}
@@ -44,7 +45,7 @@ def gi(H, f, A, b, rule, tol=1e-10, trace=None):
             if np.isfinite(t2): s = s + t * (Dc[:, q:] @ d2)
             lam = lam - t * r; up += t
             if trace is not None:
-                trace.append((q, 'add' if t2 <= t1 else 'drop'))
+                trace.append((q, 'add', -1) if t2 <= t1 else (q, 'drop', k))
             if t2 <= t1:
                 nrm = np.linalg.norm(d2)
                 alpha = -nrm if d2[0] <= 0 else nrm      # kernel: Dpq <= 0 -> -|d2|
