@@ -117,6 +117,49 @@ extern "C" int qpb_solve(const qpb_desc *d, const double *H, const double *f, co
                       qpb::optional(b, d->m), x, lam, active, status, iters, (hipStream_t)stream, "qpb_solve launch");
 }
 
+// qpb_solve_eq's own argument rules, after check_desc: the flags select
+// nothing here, and with meq > 0 the shape must have an EQ kernel form
+static int check_eq(const qpb_desc *d, int32_t meq) {
+  if (meq < 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_eq: meq < 0");
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_eq: flags must be 0 (got %d)", d->flags);
+  if (meq > 0 && qpb::route_eq(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_solve_eq: n=%d m=%d outside the kernels with equality rows (n<=%d, m<=%d)",
+                d->n, d->m, qpb::kEqMaxN, qpb::kEqMaxM);
+  if (meq > d->m) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_eq: meq=%d > m=%d", meq, d->m);
+  return 0;
+}
+
+extern "C" int qpb_solve_eq(const qpb_desc *d, int32_t meq, const double *H, const double *f, const double *A,
+                            const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                            int32_t *iters, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_eq(d, meq);
+  if (rc) return rc;
+  // no equality rows: the call is qpb_solve, launch for launch
+  if (meq == 0) return qpb_solve(d, H, f, A, b, x, lam, active, status, iters, stream);
+  if (d->batch == 0) return 0;
+  rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_eq(d->n, d->m);
+  qpb_gi_eq_launcher *const fn = r.kernel == qpb::Kernel::gi_dense ? qpb_launch_gi_eq : qpb_launch_gi_wave_eq;
+  const long long n = d->n, m = d->m;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const double *fc, const double *Ac, const double *bc, double *xc,
+          double *lc, uint32_t *ac, int32_t *sc, int32_t *ic) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e = fn(&c, meq, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_eq launch");
+      },
+      qpb::required(H, n * n), qpb::required(f, n), qpb::required(A, m * n), qpb::required(b, m),
+      qpb::required(x, n), qpb::required(lam, m), qpb::required(active, (m + 31) / 32), qpb::required(status, 1),
+      qpb::optional(iters, 1));
+}
+
 extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
                              const double *ub, double *x, double *lam, uint32_t *active, int32_t *status,
                              int32_t *iters, void *stream) {
@@ -192,13 +235,11 @@ static hipError_t down(void *dst, const DevBuf &b, size_t bytes) {
     if (e_ != hipSuccess) return hip_fail(e_, what); \
   } while (0)
 
-extern "C" int qpb_solve_host(const qpb_desc *d, const double *H, const double *f, const double *A,
-                              const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
-                              int32_t *iters) {
-  int rc = check_desc(d);
-  if (rc) return rc;
+// qpb_solve_host (meq < 0) and qpb_solve_eq_host: copy in, solve, copy out
+static int solve_host(const qpb_desc *d, int32_t meq, const double *H, const double *f, const double *A,
+                      const double *b, double *x, double *lam, uint32_t *active, int32_t *status, int32_t *iters) {
   if (d->batch == 0) return 0;
-  rc = check_device();
+  int rc = check_device();
   if (rc) return rc;
   const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
   DevBuf dH, df, dA, db, dx, dl, da, ds, di;
@@ -211,8 +252,10 @@ extern "C" int qpb_solve_host(const qpb_desc *d, const double *H, const double *
   HIPCHK(alloc(da, m ? active : nullptr, B * w * 4), "active");
   HIPCHK(alloc(ds, status, B * 4), "status");
   HIPCHK(alloc(di, iters, B * 4), "iters");
-  rc = qpb_solve(d, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
-                 (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr);
+  rc = meq < 0 ? qpb_solve(d, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
+                           (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr)
+               : qpb_solve_eq(d, meq, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
+                              (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "qpb_solve_host kernel");
   HIPCHK(down(x, dx, B * n * 8), "x D2H");
@@ -221,6 +264,28 @@ extern "C" int qpb_solve_host(const qpb_desc *d, const double *H, const double *
   HIPCHK(down(status, ds, B * 4), "status D2H");
   HIPCHK(down(iters, di, B * 4), "iters D2H");
   return 0;
+}
+
+extern "C" int qpb_solve_host(const qpb_desc *d, const double *H, const double *f, const double *A,
+                              const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                              int32_t *iters) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  return solve_host(d, -1, H, f, A, b, x, lam, active, status, iters);
+}
+
+extern "C" int qpb_solve_eq_host(const qpb_desc *d, int32_t meq, const double *H, const double *f, const double *A,
+                                 const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                                 int32_t *iters) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_eq(d, meq);
+  if (rc) return rc;
+  if (d->batch > 0) {
+    rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);  // host pointers: the same rules
+    if (rc) return rc;
+  }
+  return solve_host(d, meq, H, f, A, b, x, lam, active, status, iters);
 }
 
 static int check_ref(const qpb_ref_desc *d) {
@@ -363,4 +428,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.12 (gfx950; gi_dense v11.6: DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather on premultiplied row offsets, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.13 (gfx950; gi_dense v11.6: DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather on premultiplied row offsets, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out)"; }

@@ -126,6 +126,19 @@ __device__ __forceinline__ double rsq1(double x) {
   return y * __builtin_fma(-0.5 * x * y, y, 1.5);
 }
 
+// The state the EQ kernel forms (qpb_solve_eq) add to a QP's active-set loop;
+// empty in the other forms, which name it only in discarded statements.
+template <bool EQ>
+struct EqState {};
+template <>
+struct EqState<true> {
+  int next = 0;       // the next equality row to take (they go first, in index order)
+  int q = 0;          // equalities in the active set: positions 0 .. q-1, never dropped
+  bool sel = false;   // this trip's row p is an equality just taken
+  bool flip = false;  // ... and was negated (it was met on its a x < b side)
+  bool pneg = false;  // per lane: the row at this active position was negated
+};
+
 constexpr double kBig = 1.7976931348623157e308;  // DBL_MAX: the "no candidate" key
 
 // min-reduction key: a finite double whose low 6 mantissa bits carry a lane

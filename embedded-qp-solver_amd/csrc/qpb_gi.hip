@@ -101,13 +101,22 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 // MR: rows of D per lane (m <= 16 MR).  N16: n == 16 (coalesced loads).
 // FULL: n == 16 and m == 16 MR (no padding rows: no masking anywhere).
 // One group = the 4 QPs of a wavefront; `grp` its index.
-template <int MR, bool N16, bool FULL, bool STAMP>
+// EQ (qpb_solve_eq): rows 0 .. meq-1 are equalities a x = b.  They enter the
+// active set first, in index order, and never leave it: row p's sign is
+// chosen when it is selected (s_p > 0: row p of D and s_p are negated in
+// place, the position remembers it), after which it is an ordinary violated
+// row with s_p <= 0 and a free multiplier.  They hold the active positions
+// 0 .. eqs.q-1, which the ratio test leaves out, so a DROP never touches them.
+// A row that depends on the equalities before it is left out (bit clear,
+// lam = 0) when its residual is within the tolerance, else the QP is
+// INFEASIBLE.  The finish writes lam and x with the caller's signs.
+template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
     uint32_t *__restrict__ actg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m,
     long long batch, int max_iter, double feas_tol, int flags, unsigned long long *__restrict__ dbg,
-    long long grp) {
+    long long grp, [[maybe_unused]] int meq = 0) {
   static_assert(!FULL || N16, "FULL implies n == 16");
   SectionClock<STAMP> clk;
   const int l = threadIdx.x & (NL - 1);
@@ -185,6 +194,14 @@ __device__ __forceinline__ void gi_group(
     bl[r] = ok ? (bv[r] == bv[r] ? bv[r] : kInf) : 0.0;
     thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
     infeasible_row = infeasible_row || (ok && nrm2 == 0.0 && bl[r] < -feas_tol * (1.0 + __builtin_fabs(bl[r])));
+    if constexpr (EQ) {
+      // an equality: a zero row is infeasible for b of either sign, and a
+      // non-finite b cannot mean "absent" -- QPB_NUMERICAL through the NaN
+      // threshold, like a NaN row
+      const bool eqr = ok && l + NL * r < meq;
+      infeasible_row = infeasible_row || (eqr && nrm2 == 0.0 && bl[r] > feas_tol * (1.0 + __builtin_fabs(bl[r])));
+      thr[r] = (eqr && !(__builtin_fabs(bv[r]) < kInf)) ? __builtin_nan("") : thr[r];
+    }
     act[r] = false;
   };
   if constexpr (N16) {
@@ -359,11 +376,22 @@ __device__ __forceinline__ void gi_group(
   int p = 0;
   double up = 0.0;  // multiplier of the constraint being added
   int it = 0;
+  [[maybe_unused]] EqState<EQ> eqs;
   wave_lds_sync();
   clk.tick(3);
 
   while (!done && it < max_iter) {
     ++it;
+    if constexpr (EQ) {
+      // the equality phase: one row per trip, whatever its slack (it ends in
+      // an ADD or leaves the row out, never in a partial step)
+      eqs.sel = selecting && eqs.next < meq;
+      if (eqs.sel) {
+        p = eqs.next++;
+        up = 0.0;
+        selecting = false;
+      }
+    }
     if (selecting) {
       // The violation test is fp64 on the slack normalised by |a_row| (the
       // feasibility tolerance); among the violated rows the argmax runs on
@@ -381,7 +409,10 @@ __device__ __forceinline__ void gi_group(
         // when the ratio underflows (row 0 included)
         const float kf = __builtin_fmaf((float)(-s[r]), __builtin_amdgcn_rsqf(fn2[r]), 0x1p-100f);
         const uint32_t kr = (__float_as_uint(kf) & ~31u) | (uint32_t)(l + NL * r);
-        key = viol && kr > key ? kr : key;
+        if constexpr (EQ)  // the equalities had their turn
+          key = viol && kr > key && l + NL * r >= meq ? kr : key;
+        else
+          key = viol && kr > key ? kr : key;
       }
       key = row_max_u32(key);
       if (key == 0u) {
@@ -402,6 +433,24 @@ __device__ __forceinline__ void gi_group(
     // keeps its entry D[p][l] (d = -D[p,:] in G-I's sign convention; the
     // signs are folded into the formulas below)
     const int owner = p & (NL - 1), prow = p >> 4;
+    if constexpr (EQ) {
+      // an equality met on its a x < b side becomes -a x <= -b: row p of D and
+      // s_p change sign in place, and the QP's lanes learn of it
+      if (eqs.sel) {
+        uint32_t neg = 0u;
+        if (l == owner) {
+#pragma unroll
+          for (int r = 0; r < MR; ++r)
+            if (r == prow && s[r] > 0.0) {
+#pragma unroll
+              for (int j = 0; j < NL; ++j) E[r][j] = -E[r][j];
+              s[r] = -s[r];
+              neg = 1u;
+            }
+        }
+        eqs.flip = row_max_u32(neg) != 0u;
+      }
+    }
     if (l == owner) {
 #pragma unroll
       for (int r = 0; r < MR; ++r)
@@ -458,13 +507,35 @@ __device__ __forceinline__ void gi_group(
       // the exact minimum ratio; a DROP then takes the lowest position attaining it
       const double ratio = um * rcp1(rm);
       const bool cand = l < q && rm > 0.0;
-      t1 = row_min_raw(cand ? ratio : kBig);
-      attains = cand && ratio == t1;
+      if constexpr (EQ) {  // an equality is never dropped
+        const bool cdrop = cand && l >= eqs.q;
+        t1 = row_min_raw(cdrop ? ratio : kBig);
+        attains = cdrop && ratio == t1;
+      } else {
+        t1 = row_min_raw(cand ? ratio : kBig);
+        attains = cand && ratio == t1;
+      }
     }
     const double ir = rsq1(nd2);  // 1/|d2| (only used when nd2 > 0)
     const double t2 = (nd2 > kDepTol * dd) ? -sp * (ir * ir) : kBig;
     const double t = t1 < t2 ? t1 : t2;
     if (!(t < kBig)) {
+      if constexpr (EQ) {
+        // an equality that depends on those before it (or a zero row, or any
+        // row once q = n): its residual |a x - b| can no longer change; within
+        // the tolerance the row is left out and the solve goes on
+        if (eqs.sel) {
+          uint32_t within = 0u;
+#pragma unroll
+          for (int r = 0; r < MR; ++r)
+            within |= (l == owner && r == prow && __builtin_fabs(s[r]) <= -thr[r]) ? 1u : 0u;
+          if (row_max_u32(within) != 0u) {
+            selecting = true;
+            wave_lds_sync();
+            continue;
+          }
+        }
+      }
       status = QPB_INFEASIBLE;
       done = true;
       break;
@@ -524,9 +595,11 @@ __device__ __forceinline__ void gi_group(
         invRd = ia;
         iam = p;
         um = up;
+        if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
       }
 #pragma unroll
       for (int r = 0; r < MR; ++r) act[r] = act[r] || (l == owner && r == prow);
+      if constexpr (EQ) eqs.q += eqs.sel ? 1 : 0;
       ++q;
       selecting = true;
       clk.tick(8);
@@ -621,6 +694,8 @@ __device__ __forceinline__ void gi_group(
     wave_lds_sync();
   }
   clk.tick(10);
+  // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
+  if constexpr (EQ) um = eqs.pneg ? -um : um;
 
   // ------------------------------------------------------------- outputs
   // (the active rows of A re-read, one coalesced 128-B row per active position)
@@ -773,6 +848,19 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_kernel(
 #endif
 }
 
+// qpb_solve_eq's form of the kernel: gi_group with EQ, rows 0 .. meq-1 equalities
+constexpr int kEqOcc = 3;  // waves per SIMD the EQ forms are built for
+template <int MR, bool N16, bool FULL, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_eq_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
+    const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
+    uint32_t *__restrict__ actg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, int meq,
+    long long batch, int max_iter, double feas_tol) {
+  __shared__ double lds[QPB * SLOT];
+  gi_group<MR, N16, FULL, false, true>(lds, Hg, fg, Ag, bg, xg, lamg, actg, statg, itg, n, m, batch, max_iter,
+                                       feas_tol, 0, nullptr, blockIdx.x, meq);
+}
+
 }  // namespace qpb
 
 // launcher used by qpb_api.hip
@@ -796,6 +884,30 @@ extern "C" hipError_t qpb_launch_gi(const qpb_desc *d, const double *H, const do
     else QPB_GI_LAUNCH(2, false, false);
   }
 #undef QPB_GI_LAUNCH
+  return hipGetLastError();
+}
+
+// qpb_solve_eq, n <= 16 and m <= 32: the same six forms with equality rows
+extern "C" hipError_t qpb_launch_gi_eq(const qpb_desc *d, int meq, const double *H, const double *f, const double *A,
+                                       const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                                       int32_t *iters, hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+#define QPB_GI_EQ_LAUNCH(MR, N16, FULL)                                                                          \
+  hipLaunchKernelGGL((qpb::gi_dense_eq_kernel<MR, N16, FULL, qpb::kEqOcc>), dim3((unsigned)blocks), dim3(64), \
+                     0, stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, meq, (long long)d->batch, \
+                     max_iter, tol)
+  const bool n16 = d->n == 16;
+  if (d->m <= 16) {
+    if (n16 && d->m == 16) QPB_GI_EQ_LAUNCH(1, true, true);
+    else if (n16) QPB_GI_EQ_LAUNCH(1, true, false);
+    else QPB_GI_EQ_LAUNCH(1, false, false);
+  } else {
+    if (n16 && d->m == 32) QPB_GI_EQ_LAUNCH(2, true, true);
+    else if (n16) QPB_GI_EQ_LAUNCH(2, true, false);
+    else QPB_GI_EQ_LAUNCH(2, false, false);
+  }
+#undef QPB_GI_EQ_LAUNCH
   return hipGetLastError();
 }
 

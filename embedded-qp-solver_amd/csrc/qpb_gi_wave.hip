@@ -80,13 +80,28 @@ __device__ __forceinline__ void dpp_ready2(double a, double b) { asm volatile("s
 // one QP per wavefront; MR = 1 (m <= 64); OCC waves per SIMD
 // REDO: solve only the QPs the mixed-precision kernel marked (status
 // kRedoStatus, qpb_gi_mixed.hip); every other wave exits at once
-template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false>
+// EQ (qpb_solve_eq, see qpb_gi.hip): rows 0 .. meq-1 are equalities, taken
+// first and in index order, never dropped (active positions 0 .. eqs.q-1), with
+// row p's sign chosen when it is selected and undone in lam and x at the end.
+//
+// The EQ form's `m` argument carries both counts, m | meq << kEqShift: the
+// kernel's signature, and with it the other forms' code objects, stay as they
+// were (only the template argument list in their names grew).
+constexpr int kEqShift = 16;
+static_assert(QPB_MAX_M < (1 << kEqShift));
+template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
     double feas_tol, unsigned long long *__restrict__ dbg = nullptr) {
+  static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
   __shared__ double lds[SLOT];
+  [[maybe_unused]] int meq = 0;
+  if constexpr (EQ) {
+    meq = m >> kEqShift;
+    m &= (1 << kEqShift) - 1;
+  }
   SectionClock<STAMP> clk;
   const int l = threadIdx.x;
   const long long g = blockIdx.x;
@@ -328,14 +343,41 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   bool act = false;
   int status = !spd ? QPB_NOT_SPD : (nan0 ? QPB_NUMERICAL : infeasible0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
   bool done = !spd || infeasible0 || nan0;
+  if constexpr (EQ) {
+    // an equality's zero row is infeasible for b of either sign, and its
+    // non-finite b cannot mean "absent": QPB_NUMERICAL (same precedence)
+    const bool inf_eq = wave_any(l < meq && nrm2 == 0.0 && bl > feas_tol * (1.0 + __builtin_fabs(bl)));
+    const bool nan_eq = wave_any(l < meq && !(__builtin_fabs(bv) < kInf));
+    if (spd && !nan0 && (nan_eq || (inf_eq && !infeasible0))) status = nan_eq ? QPB_NUMERICAL : QPB_INFEASIBLE;
+    done = done || nan_eq || inf_eq;
+  }
   bool selecting = true;
   int p = 0;
   double up = 0.0;
   int it = 0;
+  [[maybe_unused]] EqState<EQ> eqs;
   wave_lds_sync();
   clk.tick(2);  // L store, s, |D row|^2
   while (!done && it < max_iter) {
     ++it;
+    if constexpr (EQ) {
+      // the equality phase: one row per trip, whatever its slack (it ends in
+      // an ADD or leaves the row out, never in a partial step)
+      eqs.sel = selecting && eqs.next < meq;
+      if (eqs.sel) {
+        p = eqs.next++;
+        up = 0.0;
+        selecting = false;
+        // met on its a x < b side it becomes -a x <= -b: row p of D and s_p
+        // change sign in place
+        eqs.flip = __ballot(l == p && s > 0.0) != 0;
+        if (eqs.flip && l == p) {
+#pragma unroll
+          for (int j = 0; j < NP; ++j) E[j] = -E[j];
+          s = -s;
+        }
+      }
+    }
     if (selecting) {
       // dual steepest edge as in qpb_gi.hip: the most violated row by
       // -s / |D[l, q:]| (fp32), the row in the low 6 bits (0 = none violated)
@@ -344,6 +386,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
       // row's key nonzero when the ratio underflows or fn2 overflows)
       const float kf = __builtin_fmaf((float)(-s), __builtin_amdgcn_rsqf(fn2), 0x1p-100f);
       uint32_t kk = viol ? ((__float_as_uint(kf) & ~63u) | (uint32_t)l) : 0u;
+      if constexpr (EQ) kk = l >= meq ? kk : 0u;  // the equalities had their turn
       kk = row_max_u32(kk);
       const uint32_t k0 = __builtin_amdgcn_readlane(kk, 0), k1 = __builtin_amdgcn_readlane(kk, 16);
       const uint32_t k2 = __builtin_amdgcn_readlane(kk, 32), k3 = __builtin_amdgcn_readlane(kk, 48);
@@ -418,7 +461,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     int k = 0;
     if (q > 0) {
       const double ratio = um * rcp(rm);
-      const bool cand = l < q && rm > 0.0;
+      const bool cand = [&] {
+        if constexpr (EQ) return l >= eqs.q && l < q && rm > 0.0;  // an equality is never dropped
+        else return l < q && rm > 0.0;
+      }();
       // the reduction only when a candidate ratio is below t2 (a partial step);
       // otherwise the QP adds p and t1 stays kBig (as qpb_gi.hip)
       if (__ballot(cand && ratio < t2)) {
@@ -431,6 +477,15 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     }
     const double t = t1 < t2 ? t1 : t2;
     if (!(t < kBig)) {
+      if constexpr (EQ) {
+        // an equality that depends on those before it (or a zero row, or any
+        // row once q = n): its residual can no longer change; within the
+        // tolerance the row is left out and the solve goes on
+        if (eqs.sel && __builtin_fabs(sp) <= -readlane_d(thr, p)) {
+          selecting = true;
+          continue;
+        }
+      }
       status = QPB_INFEASIBLE;
       break;
     }
@@ -487,7 +542,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
         rdg = alpha;
         iam = p;
         um = up;
+        if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
       }
+      if constexpr (EQ) eqs.q += eqs.sel ? 1 : 0;
       if (li == q) ninvA = -ia;
       if (li + NH == q) ninvB = -ia;
       if (l == p) act = true;
@@ -578,6 +635,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // L^T x = -y lane-parallel (L read from LDS, broadcasts by v_readlane)
   double gl = fl;
   const int ll = l & (NP - 1);
+  // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
+  if constexpr (EQ) um = eqs.pneg ? -um : um;
   double *lamb = R;  // lambda by row (64 entries over the dead R)
   if constexpr (BOX) {
     // a_k = +e_k (k < n) or -e_{k-n}: g_l = f_l + lam[l] - lam[n + l], the
@@ -720,6 +779,17 @@ extern "C" hipError_t qpb_launch_gi_wave_redo(const qpb_desc *d, const double *H
                                               const double *b, double *x, double *lam, uint32_t *active,
                                               int32_t *status, int32_t *iters, hipStream_t stream) {
   return launch_gi_wave<2, false, true>(d, H, f, A, b, x, lam, active, status, iters, stream);
+}
+
+// qpb_solve_eq for the n <= 32, m <= 64 class: rows 0 .. meq-1 are equalities
+extern "C" hipError_t qpb_launch_gi_wave_eq(const qpb_desc *d, int meq, const double *H, const double *f,
+                                            const double *A, const double *b, double *x, double *lam,
+                                            uint32_t *active, int32_t *status, int32_t *iters, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true>), dim3((unsigned)d->batch), dim3(64), 0,
+                     stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m | (meq << qpb::wv::kEqShift),
+                     (long long)d->batch, max_iter, tol, nullptr);
+  return hipGetLastError();
 }
 
 // qpb_solve_box for 16 < n <= 32 (m = 2n): A = [I; -I], b = [ub; -lb] implicit

@@ -26,6 +26,12 @@ QPB_LAUNCHER qpb_gi_launcher qpb_launch_gi,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_box,                       // lb <= x <= ub, n <= 16 (qpb_gi_box.hip)
     qpb_launch_gi_wave_box,                  // ... n <= 32 (qpb_gi_wave.hip)
     qpb_launch_gi_gram_box;                  // ... n <= 128 (qpb_gi_gram.hip)
+// qpb_solve_eq: rows 0 .. meq-1 of A are equalities (1 <= meq <= d->m, d->flags == 0)
+typedef hipError_t qpb_gi_eq_launcher(const qpb_desc *d, int meq, const double *H, const double *f, const double *A,
+                                      const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
+                                      int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_eq_launcher qpb_launch_gi_eq,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_eq;                         // n <= 32, m <= 64 (qpb_gi_wave.hip)
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

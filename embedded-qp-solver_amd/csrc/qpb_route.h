@@ -69,6 +69,25 @@ static_assert(step_of(Kernel::gi_box) == 1LL << 27 && step_of(Kernel::gi_wave_bo
               step_of(Kernel::gi_gram_box) == 1LL << 25);
 static_assert(route(32, 65, 0, false).step == 1LL << 21 && route(33, 66, 0, true).step == 1LL << 25);
 
+// qpb_solve_eq with meq > 0: the EQ forms of the two wavefront-level classes,
+// whatever the flags (the call accepts none).  Above them -- the n <= 128 Gram
+// class -- there is no EQ form yet: step 0, and the call is unsupported.
+constexpr Route route_eq(int n, int m) {
+  if (n <= 16 && m <= 32) return {Kernel::gi_dense, step_of(Kernel::gi_dense)};
+  if (n <= 32 && m <= 64) return {Kernel::gi_wave, step_of(Kernel::gi_wave)};
+  return {Kernel::gi_gram, 0};
+}
+constexpr int kEqMaxN = 32, kEqMaxM = 64;  // the limit route_eq's step 0 stands for
+
+static_assert(route_eq(16, 32).kernel == Kernel::gi_dense && route_eq(1, 1).kernel == Kernel::gi_dense);
+static_assert(route_eq(16, 33).kernel == Kernel::gi_wave && route_eq(17, 1).kernel == Kernel::gi_wave);
+static_assert(route_eq(32, 64).kernel == Kernel::gi_wave && route_eq(32, 64).step == 1LL << 25);
+static_assert(route_eq(16, 32).step == 1LL << 27);
+static_assert(route_eq(33, 0).step == 0 && route_eq(32, 65).step == 0 && route_eq(16, 65).step == 0 &&
+              route_eq(128, 256).step == 0);
+static_assert(route_eq(kEqMaxN, kEqMaxM).step > 0 && route_eq(kEqMaxN + 1, 1).step == 0 &&
+              route_eq(1, kEqMaxM + 1).step == 0);
+
 // One array of a batched call: per_qp elements per QP from base.  Only an
 // optional array may be NULL, and then it is NULL in every chunk.
 template <class T>

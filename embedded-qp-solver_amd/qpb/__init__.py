@@ -11,6 +11,7 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
 
     solve(H, f, A, b)          -> qpb_solve       (active set, m > 0)
     solve(H, f)                -> qpb_solve, m=0  (test/qp_ref.py:35 semantics)
+    solve_eq(H, f, A, b, meq)  -> qpb_solve_eq    (rows 0 .. meq-1 of A are equalities)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
     ref_generate(n, B, seed)   -> qpb_ref_generate (the reference generator, bit for bit)
@@ -64,6 +65,10 @@ _lib.qpb_solve.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve.restype = ctypes.c_int
 _lib.qpb_solve_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
 _lib.qpb_solve_host.restype = ctypes.c_int
+_lib.qpb_solve_eq.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
+_lib.qpb_solve_eq.restype = ctypes.c_int
+_lib.qpb_solve_eq_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 9
+_lib.qpb_solve_eq_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
 _lib.qpb_ref_solve.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 6
@@ -132,6 +137,21 @@ def _empty_solution(B: int, n: int, m: int, dev) -> Solution:
                     torch.empty((B,), dtype=torch.int32, device=dev))
 
 
+def _solve_shape(who: str, H, f, A, b):
+    """The argument checks solve and solve_eq share: (B, n, m) of contiguous float64 CUDA tensors."""
+    import torch
+    if not (H.is_cuda and f.is_cuda):
+        raise ValueError(f"{who} expects CUDA (HIP) tensors; use solve_host for numpy")
+    B, n = f.shape
+    m = 0 if A is None else A.shape[1]
+    for t in (H, f) + ((A, b) if m else ()):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+    if H.shape != (B, n, n) or (m and (A.shape != (B, m, n) or b.shape != (B, m))):
+        raise ValueError("shape mismatch")
+    return B, n, m
+
+
 def solve(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0, out: Solution | None = None,
           stream=None, flags: int = 0) -> Solution:
     """Batched min 1/2 x^T H x + f^T x s.t. A x <= b on the GPU (torch CUDA float64 tensors).
@@ -142,16 +162,7 @@ def solve(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0, out
     passed here).  A/b omitted -> unconstrained solve.
     ``flags``: QPB_FLAG_DIAG_* kernel variants (measurement only, qpb.h).
     """
-    import torch
-    if not (H.is_cuda and f.is_cuda):
-        raise ValueError("qpb.solve expects CUDA (HIP) tensors; use solve_host for numpy")
-    B, n = f.shape
-    m = 0 if A is None else A.shape[1]
-    for t in (H, f) + ((A, b) if m else ()):
-        if t.dtype != torch.float64 or not t.is_contiguous():
-            raise ValueError("inputs must be contiguous float64")
-    if H.shape != (B, n, n) or (m and (A.shape != (B, m, n) or b.shape != (B, m))):
-        raise ValueError("shape mismatch")
+    B, n, m = _solve_shape("qpb.solve", H, f, A, b)
     if out is None:
         out = _empty_solution(B, n, m, f.device)
     d = Desc(n, m, B, max_iter, flags, feas_tol)
@@ -159,6 +170,26 @@ def solve(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0, out
                         _ptr(out.x), _ptr(out.lam), _ptr(out.active), _ptr(out.status), _ptr(out.iters),
                         _stream_ptr(stream))
     _check(rc, "qpb_solve")
+    return out
+
+
+def solve_eq(H, f, A, b, meq: int, *, max_iter: int = 0, feas_tol: float = 0.0, out: Solution | None = None,
+             stream=None) -> Solution:
+    """Batched min 1/2 x^T H x + f^T x s.t. A[:meq] x = b[:meq], A[meq:] x <= b[meq:]
+    on the GPU (qpb_solve_eq; torch CUDA float64 tensors as for ``solve``).
+
+    For ``solve_qp(P, q, G, h, A, b)`` pass the stacked ``[A; G]``, ``[b; h]``
+    and ``meq = rows(A)``.  ``lam[:, :meq]`` has either sign.  meq > 0 needs
+    n <= 32 and m <= 64; meq == 0 is ``solve``.
+    """
+    B, n, m = _solve_shape("qpb.solve_eq", H, f, A, b)
+    if out is None:
+        out = _empty_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_eq(ctypes.byref(d), int(meq), _ptr(H), _ptr(f), _ptr(A) if m else None,
+                           _ptr(b) if m else None, _ptr(out.x), _ptr(out.lam), _ptr(out.active), _ptr(out.status),
+                           _ptr(out.iters), _stream_ptr(stream))
+    _check(rc, "qpb_solve_eq")
     return out
 
 
@@ -200,6 +231,15 @@ def solve_raw(desc: Desc, ptrs, stream_ptr) -> int:
 
 def solve_host(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0) -> Solution:
     """numpy in / numpy out (qpb_solve_host: H2D, solve, D2H)."""
+    return _solve_host(None, H, f, A, b, max_iter, feas_tol)
+
+
+def solve_eq_host(H, f, A, b, meq: int, *, max_iter: int = 0, feas_tol: float = 0.0) -> Solution:
+    """numpy in / numpy out (qpb_solve_eq_host): ``solve_eq`` with host arrays."""
+    return _solve_host(int(meq), H, f, A, b, max_iter, feas_tol)
+
+
+def _solve_host(meq, H, f, A, b, max_iter, feas_tol) -> Solution:
     import numpy as np
     H = np.ascontiguousarray(H, dtype=np.float64)
     f = np.ascontiguousarray(f, dtype=np.float64)
@@ -216,8 +256,12 @@ def solve_host(H, f, A=None, b=None, *, max_iter: int = 0, feas_tol: float = 0.0
     it = np.zeros(B, dtype=np.int32)
     d = Desc(n, m, B, max_iter, 0, feas_tol)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
-    rc = _lib.qpb_solve_host(ctypes.byref(d), p(H), p(f), p(A), p(b), p(x), p(lam), p(act), p(st), p(it))
-    _check(rc, "qpb_solve_host")
+    if meq is None:
+        rc = _lib.qpb_solve_host(ctypes.byref(d), p(H), p(f), p(A), p(b), p(x), p(lam), p(act), p(st), p(it))
+        _check(rc, "qpb_solve_host")
+    else:
+        rc = _lib.qpb_solve_eq_host(ctypes.byref(d), meq, p(H), p(f), p(A), p(b), p(x), p(lam), p(act), p(st), p(it))
+        _check(rc, "qpb_solve_eq_host")
     return Solution(x, lam, act, st, it)
 
 

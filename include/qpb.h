@@ -11,6 +11,7 @@
  *                      admm (box = config.h:29-30)       qpb_ref_solve(QPB_REF_ADMM)
  *   test/qp_ref.py:35  solve_qp(P, q, G=0, h=0)          qpb_solve(m = 0)
  *   north_star active-set over (H, f, A, b)              qpb_solve(m > 0)
+ *   ... with equality rows, solve_qp(P, q, G, h, A, b)    qpb_solve_eq
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -66,6 +67,35 @@
  * absent, exactly as b = +inf (the box bounds of qpb_solve_box likewise).
  * feas_tol: row i counts as violated when a_i x - b_i > feas_tol (|a_i| + |b_i|).
  *
+ * Equality rows (qpb_solve_eq; rows 0 .. meq-1 of A are a_i x = b_i).  The two
+ * sentences above on what is written and on what a QP's outputs depend on
+ * hold unchanged, and so does everything not restated here:
+ *   lam             lam[i] of an equality has either sign; lam >= 0 is promised
+ *                   for the rows >= meq only (so read at QPB_MAX_ITER too).
+ *                   H x + f + A^T lam = 0 holds with the caller's A as given.
+ *   dependent row   an equality that depends linearly on the equalities taken
+ *                   before it (|d2|^2 <= 1e-24 |D_p|^2, the kernels' test; a
+ *                   zero row, and any row once n independent ones are in) is
+ *                   left out when |a_i x - b_i| <= feas_tol (|a_i| + |b_i|):
+ *                   its bit stays clear, lam[i] = 0, and the solve goes on --
+ *                   the residual cannot change later, the rows it depends on
+ *                   are never dropped.  Which rows of a dependent set are kept
+ *                   is unspecified; the set bits among the rows < meq number
+ *                   rank(E).  With a residual outside the tolerance the QP is
+ *                   QPB_INFEASIBLE (found by the iteration).
+ *   zero row        an equality's zero row is infeasible iff
+ *                   |b_i| > feas_tol (1 + |b_i|) (the set-up's rule with both
+ *                   signs: iters = 0, lam = 0, active = 0).
+ *   inequalities    a violated inequality that depends on the active rows with
+ *                   no inequality among them to drop gives QPB_INFEASIBLE, as
+ *                   before: an equality is never dropped.
+ *   non-finite b    NaN or +-Inf in b_i of an equality gives QPB_NUMERICAL
+ *                   from the set-up (iters = 0, lam = 0, active = 0): an
+ *                   equality cannot be absent.  In a row >= meq a NaN still
+ *                   means the row is absent.
+ *   iterations      each equality taken or left out is one iteration; the
+ *                   default max_iter stays 4 (n + m) + 8.
+ *
  * All array pointers passed to qpb_solve / qpb_ref_solve are DEVICE pointers
  * (hipMalloc'd or torch CUDA tensors) and the call is asynchronous on
  * `stream` (a hipStream_t, NULL = default stream).  The *_host variants take
@@ -85,7 +115,7 @@ extern "C" {
 
 /* qpb_version() reports "qpb MAJOR.MINOR (...)" */
 #define QPB_VERSION_MAJOR 0
-#define QPB_VERSION_MINOR 12
+#define QPB_VERSION_MINOR 13
 
 /* limits of this build's kernels: n <= 16, m <= 32 one QP per 16-lane DPP
  * row (qpb_gi.hip); n <= 32, m <= 64 one QP per wavefront (qpb_gi_wave.hip);
@@ -163,6 +193,32 @@ int qpb_solve(const qpb_desc *desc, const double *H, const double *f,
 int qpb_solve_host(const qpb_desc *desc, const double *H, const double *f,
 		   const double *A, const double *b, double *x, double *lam,
 		   uint32_t *active, int32_t *status, int32_t *iters);
+
+/* qpb_solve with equality rows: rows 0 .. meq-1 of A are a_i x = b_i, rows
+ * meq .. m-1 are a_i x <= b_i (Goldfarb and Idnani's, and quadprog's, meq; for
+ * solve_qp(P, q, G, h, A, b) stack [A; G], [b; h] and pass meq = rows(A)).
+ * The method takes the equalities first and never drops them; their
+ * multipliers are free in sign (the status contract above has the details).
+ *   meq < 0, meq > m or desc->flags != 0   QPB_ERR_INVALID_ARG (the diagnostic
+ *                   flags and QPB_FLAG_MIXED select nothing here)
+ *   meq == 0        the call is qpb_solve: every shape, the same launches,
+ *                   the same outputs bit for bit
+ *   meq > 0         n <= 32 and m <= 64 (the EQ forms of qpb_gi.hip and
+ *                   qpb_gi_wave.hip); above that QPB_ERR_UNSUPPORTED, which
+ *                   is tested before meq > m.  The n <= 128 class
+ *                   (qpb_gi_gram.hip) has no equality form yet: a follow-up.
+ * Pointers, batch == 0 and a missing device as qpb_solve; qpb_desc is
+ * unchanged, which is why meq is an argument. */
+int qpb_solve_eq(const qpb_desc *desc, int32_t meq, const double *H,
+		 const double *f, const double *A, const double *b, double *x,
+		 double *lam, uint32_t *active, int32_t *status, int32_t *iters,
+		 void *stream);
+
+/* Same with host pointers, as qpb_solve_host. */
+int qpb_solve_eq_host(const qpb_desc *desc, int32_t meq, const double *H,
+		      const double *f, const double *A, const double *b,
+		      double *x, double *lam, uint32_t *active, int32_t *status,
+		      int32_t *iters);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
