@@ -141,6 +141,18 @@ struct EqState<true> {
 
 constexpr double kBig = 1.7976931348623157e308;  // DBL_MAX: the "no candidate" key
 
+// The multiplier an inequality's active position is written with.  In exact
+// arithmetic the ratio test keeps every multiplier >= 0.  When two of them
+// reach zero in the same partial step (duplicated rows, a degenerate vertex)
+// only one position is dropped; the other keeps um - t rm = -(a few ulp) --
+// the step is lane k's ratio, rounded, and the packed keys pick k within
+// 63 ulp -- and stays that way if no later step moves it.  qpb.h promises
+// lam >= 0: such a multiplier is written as 0, and x is recovered from the
+// multipliers as written, so stationarity holds as before.  Applied once,
+// after the loop.  Values >= 0 and -0.0 pass unchanged (non-degenerate solves
+// keep their bits), and so does a NaN (the comparison is false).
+__device__ __forceinline__ double dual_out(double u) { return u < 0.0 ? 0.0 : u; }
+
 // min-reduction key: a finite double whose low 6 mantissa bits carry a lane
 // index (value perturbed by <= 63 ulp).  v_min_f64 over the lanes then yields
 // the minimum and its index together, 3 instructions per DPP step.

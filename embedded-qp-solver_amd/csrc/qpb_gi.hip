@@ -696,6 +696,9 @@ __device__ __forceinline__ void gi_group(
   clk.tick(10);
   // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
   if constexpr (EQ) um = eqs.pneg ? -um : um;
+  // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
+  if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
+  else um = dual_out(um);
 
   // ------------------------------------------------------------- outputs
   // (the active rows of A re-read, one coalesced 128-B row per active position)

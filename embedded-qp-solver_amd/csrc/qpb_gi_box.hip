@@ -387,7 +387,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   lamb[l] = 0.0;
   lamb[l + NL] = 0.0;
   wave_lds_sync();
-  if (l < q && iam >= 0) lamb[iam] = um;
+  if (l < q && iam >= 0) lamb[iam] = dual_out(um);  // lam >= 0: a tie's -eps written as 0
   wave_lds_sync();
   const double lu = lamb[l], ll = lamb[l + NL];
   wave_lds_sync();

@@ -950,7 +950,7 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
     // vectors are added per column
     for (int e = tid; e < MB; e += NT) vb[e] = 0.0;
     __syncthreads();
-    if (tid < q && iamb[tid] >= 0) vb[iamb[tid]] = lamb[tid];
+    if (tid < q && iamb[tid] >= 0) vb[iamb[tid]] = dual_out(lamb[tid]);  // lam >= 0: a tie's -eps written as 0
     __syncthreads();
     {
       double lw[RT];

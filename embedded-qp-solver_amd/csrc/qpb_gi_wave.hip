@@ -637,6 +637,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   const int ll = l & (NP - 1);
   // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
   if constexpr (EQ) um = eqs.pneg ? -um : um;
+  // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
+  if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
+  else um = dual_out(um);
   double *lamb = R;  // lambda by row (64 entries over the dead R)
   if constexpr (BOX) {
     // a_k = +e_k (k < n) or -e_{k-n}: g_l = f_l + lam[l] - lam[n + l], the

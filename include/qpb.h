@@ -66,6 +66,17 @@
  * QPB_NUMERICAL, that over QPB_INFEASIBLE).  A NaN in b means the row is
  * absent, exactly as b = +inf (the box bounds of qpb_solve_box likewise).
  * feas_tol: row i counts as violated when a_i x - b_i > feas_tol (|a_i| + |b_i|).
+ * Degenerate QPs (linearly dependent rows through the solution, duplicated
+ * rows, rows that are tight with a zero multiplier, more than n tight rows, and
+ * for qpb_solve_box a pinned variable lb_j == ub_j, whose two rows are both
+ * tight) are ordinary inputs: QPB_OK, the same x, and every promise above.
+ * lam >= 0 holds exactly, not within rounding: a multiplier that a tie in the
+ * ratio test left a few ulp below zero is written as 0 and x is recovered
+ * from the multipliers as written.  Which rows of a dependent tight set carry
+ * the multipliers (and have their bit set) is unspecified; a row that is not
+ * tight never has its bit set.  For a pinned variable lam_ub[j] - lam_lb[j] is
+ * the one multiplier of x_j = lb_j, with either sign.  Pinned by
+ * tests/test_gpu_degenerate.py on every kernel route.
  *
  * Equality rows (qpb_solve_eq; rows 0 .. meq-1 of A are a_i x = b_i).  The two
  * sentences above on what is written and on what a QP's outputs depend on
