@@ -1,0 +1,634 @@
+// qpb_kkt_bwd.hip -- the backward pass of a solve (qpb_solve_backward) for gfx950.
+//
+// Given a solved QP (x, lam, the active bit mask W of a linearly independent
+// active set) and the cotangent g = dl/dx, the gradients of l with respect to
+// H, f, A and b follow from ONE solve of the KKT system at fixed active set
+//
+//     [ H    A_W^T ] [ dx   ]     [ g ]
+//     [ A_W   0    ] [ dlam ] = - [ 0 ]
+//
+//     dl/df = dx                        dl/dH   = 1/2 (dx x^T + x dx^T)
+//     dl/db_i = -dlam_i                 dl/dA_i = dlam_i x^T + lam_i dx^T   (i in W, else 0)
+//
+// H is factored, the Schur complement A_W H^{-1} A_W^T is never formed (it
+// squares the condition number): with H = L L^T, u = L^{-1} g and
+// D_W = A_W L^{-T} (the forward kernels' D), the rows of D_W are
+// orthogonalised in row order, D_W^T = Q R, and
+//
+//     z = -(u - Q Q^T u),   dx = L^{-T} z,   R dlam = -Q^T u.
+//
+// A row whose part orthogonal to the rows before it has |d2|^2 <= kDepTol |d|^2
+// (the forward's dependency test) is skipped: dlam_i = 0, it keeps only the
+// lam_i dx^T term of dl/dA_i.  The forward solve never produces such a mask.
+//
+// n <= 16, m <= 32 (kkt_bwd_dense_kernel): gi_dense's mapping, one QP per
+// 16-lane DPP row, four per wavefront.  Lane l holds row l of H -> L and rows
+// l, l + 16 of A -> D from the forward's right-looking sweep, which also
+// carries u.  The orthogonalisation keeps every vector DISTRIBUTED (lane j
+// holds component j): lane j keeps component j of every q_s in 16 statically
+// indexed registers, a trip takes the owner's row through the exchange row in
+// LDS, q_s . v is a row_sum per s and v -= sum_s c_s q_s is in-lane.  Two
+// passes per row (classical Gram-Schmidt, repeated) give MGS-grade
+// orthogonality with no dependence between the 16 products of a pass.  R's
+// column t goes to LDS as in gi_dense (column-major, zero diagonal, 1 / R_tt
+// in lane t), so both triangular solves are its lane-parallel DPP-fused back
+// substitution.
+#include "qpb_common.h"
+#include "qpb_launch.h"  // with qpb.h
+
+namespace qpb {
+namespace bwd {
+
+constexpr int NL = 16;  // lanes per QP
+constexpr int QPB = 4;  // QPs per wavefront
+constexpr int RS = 18;  // row stride of the staged 16 x 16 input blocks (conflict-free b128 rows)
+constexpr int L_SIZE = lrow(NL);  // 136
+// per QP: L packed (136) | R column-major 16 x 16 with zero diagonal (the
+// exchange row is its column 0, which the back substitution never reads).
+// After the solves the L part holds the vectors of the outer products.
+constexpr int OFF_L = 0;
+constexpr int OFF_R = L_SIZE;
+constexpr int SLOT = OFF_R + NL * NL + 2;  // 394 doubles, gi_dense's slot
+constexpr int OFF_X = 0, OFF_DX = 16, OFF_DL = 32, OFF_LM = 64;  // x, dx | dlam, masked lam (32 each)
+static_assert(NL * RS <= SLOT, "the input blocks are staged over the whole slot");
+static_assert(OFF_LM + 32 <= L_SIZE, "the output vectors fit the dead L");
+static_assert(QPB * SLOT * 8 <= kWaveLdsMax, "12 waves per CU by LDS");
+
+// p + q rounded once each and added: the value is symmetric under swapping the
+// two products, so gH == gH^T bit for bit (a contracted fma(a, b, c d) is not)
+__device__ __forceinline__ double sym2(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double p = a * b;
+  const double q = c * d;
+  return p + q;
+}
+
+// MR: rows of A per lane (m <= 16 MR).  N16: n == 16 (coalesced loads and
+// stores through this QP's LDS slot); otherwise the rows are padded with the
+// identity and padded variables take no part.
+template <int MR, bool N16>
+__global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
+    const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
+    const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
+    double *__restrict__ gbg, int n, int m, long long batch) {
+  __shared__ double lds[QPB * SLOT];
+  const int l = threadIdx.x & (NL - 1);
+  const int slot = threadIdx.x >> 4;
+  // rows past the end of the batch replay its last QP and store nothing (as
+  // in qpb_gi.hip: every lane stays live for the cross-row readlanes)
+  const long long graw = (long long)blockIdx.x * QPB + slot;
+  const bool live = graw < batch;
+  const long long g = live ? graw : batch - 1;
+  if constexpr (N16) n = NL;
+  double *base = lds + (((slot & 1) << 1) | (slot >> 1)) * SLOT;  // slots 0, 2, 1, 3 (bank spread)
+  double *Lp = base + OFF_L;
+  double *R = base + OFF_R;
+  double *xch = R;
+
+  // ------------------------------------------------------------------ load
+  const bool var = N16 || l < n;
+  const int lc = var ? l : n - 1;
+  const double *Hq = Hg + g * (long long)n * n;
+  const double *Aq = m > 0 ? Ag + g * (long long)m * n : Hq;  // m == 0: the (masked) row loads read H
+  const bool ok = statg ? statg[g] == QPB_OK : true;
+  // a QP that is not QPB_OK takes no trips and stores zeros
+  uint32_t W = (m > 0 && ok) ? actg[g] : 0u;
+  if (m < 32) W &= (1u << m) - 1u;
+  const double gv = gxg[g * n + lc];
+  double Lr[NL];     // row l of H, becomes row l of L
+  double E[MR][NL];  // rows l, l + 16 of A, become rows of D = A L^{-T}
+  if constexpr (N16) {
+    // coalesced 16-byte loads, two whole rows of each of the wave's 4 QPs per
+    // instruction; the rows reach their owner lanes through a transpose in
+    // this QP's LDS slot (qpb_gi.hip)
+    const int hr = l >> 3, hc = 2 * (l & 7);
+    auto stage = [&](const double2(&v)[8]) {
+      wave_lds_sync();
+#pragma unroll
+      for (int t = 0; t < 8; ++t) *reinterpret_cast<double2 *>(&base[(2 * t + hr) * RS + hc]) = v[t];
+      wave_lds_sync();
+    };
+    double2 hv[8], av[MR][8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) hv[t] = *reinterpret_cast<const double2 *>(&Hq[(2 * t + hr) * NL + hc]);
+#pragma unroll
+    for (int r = 0; r < MR; ++r)
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        // rows past m read a valid row (m == 0: of H) and are zeroed: no branch around a load
+        const int row = NL * r + 2 * t + hr;
+        const double2 a = *reinterpret_cast<const double2 *>(&Aq[(row < m ? row : 0) * NL + hc]);
+        asm volatile("" ::"v"(a.x), "v"(a.y));
+        av[r][t] = row < m ? a : make_double2(0.0, 0.0);
+      }
+    stage(hv);
+    lds_row16(&base[l * RS], Lr);
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      stage(av[r]);
+      lds_row16(&base[l * RS], E[r]);
+    }
+    wave_lds_sync();
+  } else {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const double h = Hq[lc * n + (j < n ? j : n - 1)];
+      Lr[j] = (l < n && j < n) ? h : (l == j ? 1.0 : 0.0);
+    }
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      const int row = l + NL * r;
+      const bool rok = row < m;
+      const int rc = rok ? row : 0;
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        const double a = Aq[rc * n + (j < n ? j : n - 1)];
+        E[r][j] = (rok && j < n) ? a : 0.0;
+      }
+    }
+  }
+
+  // ---- H = L L^T, D = A L^{-T}, u = L^{-1} g: the forward's right-looking
+  // sweep (qpb_gi.hip).  Step k: the pivot row is read straight from lane k by
+  // the DPP-fused FMAs; the sched_barrier and the rsq chain keep every write
+  // of Lr[j] and of the running g (previous step) well over two instructions
+  // before these reads.  u_k = g_k / L_kk is final at step k, on lane k.
+  double ya = var ? gv : 0.0, ul = 0.0, invLd = 0.0;
+  unroll<NL>([&](auto K) {
+    constexpr int k = K;
+    __builtin_amdgcn_sched_barrier(0);
+    const double akk = bc<k>(Lr[k]);
+    const double ik = rsq1(akk);
+    const double ik2 = ik * ik;
+    const double nc = -(Lr[k] * ik2);
+    double ne2[MR];
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      const double e = E[r][k];
+      ne2[r] = -(e * ik2);
+      E[r][k] = e * ik;
+      pin(E[r][k]);
+    }
+    // (pinned: the selects would otherwise sink past the sweep with all 16 steps' operands alive)
+    ul = l == k ? ya * ik : ul;
+    invLd = l == k ? ik : invLd;
+    pin(ul);
+    pin(invLd);
+    unroll<NL - 1 - k>([&](auto J) {
+      constexpr int j = k + 1 + J;
+#pragma unroll
+      for (int r = 0; r < MR; ++r) fmac_bc<k>(E[r][j], Lr[j], ne2[r]);
+      fmac_bc<k>(Lr[j], Lr[j], nc);
+    });
+    fmac_bc<k>(ya, ya, nc);  // lane k's own g_k becomes 0 (dead)
+    Lr[k] *= ik;
+    pin(Lr[k]);
+  });
+  __builtin_amdgcn_sched_barrier(0);
+  // L -> LDS, packed rows, for the last solve (descending j: a lane's dead
+  // entries past its diagonal land first and are overwritten by their owners)
+  unroll<NL>([&](auto J) {
+    constexpr int j = NL - 1 - J;
+    Lp[lrow(l) + j] = Lr[j];
+    wave_lds_sync();
+  });
+  // R zeroed in pairs at lane-rotated positions (qpb_gi_box.hip)
+#pragma unroll
+  for (int j = 0; j < NL; j += 2)
+    *reinterpret_cast<double2 *>(&R[l * NL + ((j + 2 * l) & (NL - 1))]) = make_double2(0.0, 0.0);
+
+  // ------------------------------------------------ D_W^T = Q R, row order
+  double Qt[NL];  // component l of q_0 .. q_15 (0 past cnt)
+#pragma unroll
+  for (int s = 0; s < NL; ++s) Qt[s] = 0.0;
+  int cnt = 0;         // independent rows so far = the next position
+  double invRd = 0.0;  // 1 / R[l][l]
+  int pos[MR];         // position of the lane's rows, -1: not in W or skipped
+#pragma unroll
+  for (int r = 0; r < MR; ++r) pos[r] = -1;
+  uint32_t rem = W;
+  // v -= sum_s (q_s . v) q_s over the positions in use by any of the wave's
+  // QPs; a QP's unused q_s are 0 and change nothing.  cl += (q_l . v).
+  auto project = [&](double &v, double &cl, int smax) {
+    const double v0 = v;
+    unroll<NL>([&](auto S) {
+      constexpr int s = S;
+      if (s < smax) {
+        const double c = row_sum(Qt[s] * v0);
+        cl += (l == s) ? c : 0.0;
+        v = __builtin_fma(-c, Qt[s], v);
+      }
+    });
+  };
+  while (wave_any(rem != 0u)) {
+    const bool valid = rem != 0u;
+    const int i = valid ? __builtin_ctz(rem) : 0;
+    rem &= rem - 1u;
+    const int owner = i & (NL - 1);
+    wave_lds_sync();
+    if (valid && l == owner) {
+#pragma unroll
+      for (int j = 0; j < NL; j += 2) {
+        double a = E[0][j], b = E[0][j + 1];
+        if constexpr (MR > 1) {
+          a = i >= NL ? E[1][j] : a;
+          b = i >= NL ? E[1][j + 1] : b;
+        }
+        *reinterpret_cast<double2 *>(&xch[j]) = make_double2(a, b);
+      }
+    }
+    wave_lds_sync();
+    double v = valid ? xch[l] : 0.0;
+    const int smax = wave_max4(cnt);
+    const double dd = row_sum(v * v);  // |d|^2
+    double cl = 0.0;                   // R[l][cnt]
+    project(v, cl, smax);
+    project(v, cl, smax);
+    const double nd2 = row_sum(v * v);  // |d2|^2
+    const bool indep = valid && cnt < NL && nd2 > kDepTol * dd;
+    const double rn = rsq(nd2);
+    if (indep) {
+      const double ql = v * rn;
+      unroll<NL>([&](auto S) {
+        constexpr int s = S;
+        Qt[s] = cnt == s ? ql : Qt[s];
+      });
+      if (cnt > 0) R[cnt * NL + l] = cl;  // column 0 has no entry above the diagonal
+      invRd = l == cnt ? rn : invRd;
+      if (l == owner) {
+        if (i < NL) pos[0] = cnt;
+        if constexpr (MR > 1)
+          if (i >= NL) pos[1] = cnt;
+      }
+      ++cnt;
+    }
+  }
+  wave_lds_sync();
+
+  // ---- z = -(u - Q Q^T u), R dlam = -Q^T u
+  const int qmax = wave_max4(cnt);
+  double z = ul, cu = 0.0;
+  project(z, cu, qmax);
+  z = -z;
+  double y;  // dlam of position l
+  {
+    const double ninv = -invRd;
+    double nacc = -cu;
+    unroll<NL>([&](auto JJ) {
+      constexpr int j = NL - 1 - JJ;
+      if (j > 0 && j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, R[j * NL + l]);
+    });
+    y = nacc * invRd;
+  }
+  // ---- L^T dx = z, the same back substitution on L's rows
+  double dx;
+  {
+    const double ninv = -invLd;
+    double nacc = z;
+    unroll<NL>([&](auto JJ) {
+      constexpr int j = NL - 1 - JJ;
+      if (j > 0) {
+        const double lj = l < j ? Lp[lrow(j) + l] : 0.0;
+        fmac_bc_nop<j>(nacc, nacc * ninv, lj);
+      }
+    });
+    dx = nacc * invLd;
+  }
+  // dlam to the rows' owners through the exchange row
+  wave_lds_sync();
+  xch[l] = y;
+  wave_lds_sync();
+  double dl[MR];
+#pragma unroll
+  for (int r = 0; r < MR; ++r) dl[r] = pos[r] >= 0 ? xch[pos[r]] : 0.0;
+  wave_lds_sync();
+
+  // ------------------------------------------------------------------ store
+  // The lane's indices are formed again from an opaque copy of the thread id:
+  // shared with the load phase, the address offsets would stay alive (spilled
+  // to scratch) across the whole kernel.  x and lam are read here for the same
+  // reason; the loads fly under the vector exchange below.
+  unsigned tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int ls = tid & (NL - 1);
+  const long long gs_raw = (long long)blockIdx.x * QPB + (tid >> 4);
+  const bool lives = gs_raw < batch;
+  const long long gs = lives ? gs_raw : batch - 1;
+  const bool vars = N16 || ls < n;
+  const double xv = xg[gs * n + (vars ? ls : n - 1)];
+  double lmv[MR];  // lam of the lane's rows, 0 outside W
+#pragma unroll
+  for (int r = 0; r < MR; ++r) {
+    const int row = ls + NL * r;
+    const double lv = m > 0 ? lamg[gs * m + (row < m ? row : 0)] : 0.0;
+    lmv[r] = ((W >> row) & 1u) ? lv : 0.0;
+  }
+  if (!ok) dx = 0.0;
+  const double xo = (ok && vars) ? xv : 0.0;
+  if (gfg && lives && vars) gfg[gs * n + ls] = dx;
+#pragma unroll
+  for (int r = 0; r < MR; ++r) {
+    const int row = ls + NL * r;
+    if (gbg && lives && row < m) gbg[gs * m + row] = pos[r] >= 0 ? -dl[r] : 0.0;
+  }
+  const bool wantA = gAg && m > 0;
+  if (!gHg && !wantA) return;  // wave-uniform
+  // the vectors of the outer products, over the dead L
+  base[OFF_X + ls] = xo;
+  base[OFF_DX + ls] = dx;
+#pragma unroll
+  for (int r = 0; r < MR; ++r) {
+    base[OFF_DL + ls + NL * r] = dl[r];
+    base[OFF_LM + ls + NL * r] = lmv[r];
+  }
+  wave_lds_sync();
+  const double *X = base + OFF_X, *DX = base + OFF_DX, *DL = base + OFF_DL, *LM = base + OFF_LM;
+  if constexpr (N16) {
+    // lane l writes columns 2 (l & 7), +1 of rows 2 t + (l >> 3): 256 contiguous bytes per QP and store
+    const int hr = ls >> 3, hc = 2 * (ls & 7);
+    const double x0 = X[hc], x1 = X[hc + 1], d0 = DX[hc], d1 = DX[hc + 1];
+    if (gHg && lives) {
+      double *o = gHg + gs * (long long)(NL * NL);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int row = 2 * t + hr;
+        const double dr = DX[row], xr = X[row];
+        *reinterpret_cast<double2 *>(&o[row * NL + hc]) =
+            make_double2(0.5 * sym2(dr, x0, xr, d0), 0.5 * sym2(dr, x1, xr, d1));
+      }
+    }
+    if (wantA && lives) {
+      double *o = gAg + gs * (long long)m * NL;
+#pragma unroll
+      for (int r = 0; r < MR; ++r)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const int row = NL * r + 2 * t + hr;
+          if (row < m) {
+            const double dr = DL[row], lr = LM[row];
+            *reinterpret_cast<double2 *>(&o[row * NL + hc]) =
+                make_double2(sym2(dr, x0, lr, d0), sym2(dr, x1, lr, d1));
+          }
+        }
+    }
+  } else {
+    // element e of the row-major output at lane e mod 16
+    if (gHg && lives) {
+      double *o = gHg + gs * (long long)n * n;
+      for (int e = ls; e < n * n; e += NL) {
+        const int row = e / n, col = e - row * n;
+        o[e] = 0.5 * sym2(DX[row], X[col], X[row], DX[col]);
+      }
+    }
+    if (wantA && lives) {
+      double *o = gAg + gs * (long long)m * n;
+      for (int e = ls; e < m * n; e += NL) {
+        const int row = e / n, col = e - row * n;
+        o[e] = sym2(DL[row], X[col], LM[row], DX[col]);
+      }
+    }
+  }
+}
+
+// ---- 16 < n <= 32 or 32 < m <= 64: one QP per wavefront ----------------------
+// The matrices live in LDS in gi_wave's manner: L in the lower triangle of a
+// 32 x 33 block (odd stride: rows and columns are both conflict-free), R above
+// its diagonal, the orthonormal rows q_s in a second block.  Lane j < 32 holds
+// component j of the running vectors; a QP is alone in its wave, so every
+// loop bound is wave-uniform.  The algebra is the dense kernel's: row i of
+// D_W = A_W L^{-T} comes from a forward substitution as it is met, in row
+// order, and is orthogonalised against the q_s before it in two passes.
+// H is padded to 32 x 32 with the identity and the unused q_s are zero, so the
+// loops over components and positions have constant bounds and unroll: their
+// LDS reads issue back to back instead of one per loop trip.
+constexpr int WN = 32;       // variables (lanes that carry a component)
+constexpr int WS = WN + 1;   // row stride
+constexpr int W_L = 0, W_Q = WN * WS, W_V = 2 * WN * WS;  // L (+ R) | Q | vectors
+// vectors: v, c, u | 1 / R_tt | position of a row (64) | x, dx | dlam, masked lam (64 each)
+constexpr int W_C = W_V + 32, W_U = W_C + 32, W_IR = W_U + 32, W_POS = W_IR + 32, W_X = W_POS + 64,
+              W_DX = W_X + 32, W_DL = W_DX + 32, W_LM = W_DL + 64, W_SIZE = W_LM + 64;
+constexpr int W_COL = WN + 2;  // the pivot column of a factorisation step, zero past the matrix
+static_assert((W_SIZE + W_COL) * 8 <= 20480, "8 waves per CU by LDS");
+
+// sum over the 64 lanes, the same bits on every lane
+__device__ __forceinline__ double wave_sum(double t) {
+  t = row_sum(t);
+  return (readlane_d(t, 0) + readlane_d(t, 16)) + (readlane_d(t, 32) + readlane_d(t, 48));
+}
+
+__global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
+    const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
+    const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
+    double *__restrict__ gbg, int n, int m, long long batch) {
+  __shared__ double lds[W_SIZE];
+  // an object of its own: the factorisation's trailing update reads it while
+  // it writes L, and the compiler can then batch the reads of an unrolled trip
+  __shared__ double colk[W_COL];
+  const int lane = threadIdx.x;
+  const int i = lane & (WN - 1), half = lane >> 5;
+  const bool low = lane < WN;      // the lanes that carry a component
+  const long long g = blockIdx.x;  // one workgroup of one wave per QP: always < batch
+  double *Lm = lds + W_L, *Qm = lds + W_Q;
+  double *vb = lds + W_V, *cb = lds + W_C, *ub = lds + W_U, *ir = lds + W_IR, *posb = lds + W_POS;
+  const double *Hq = Hg + g * (long long)n * n;
+  const double *Aq = Ag + g * (long long)m * n;
+  const bool ok = statg ? statg[g] == QPB_OK : true;
+  // the active mask as one 64-bit word (wave-uniform); a QP that is not QPB_OK takes no trips
+  const int words = (m + 31) / 32;
+  unsigned long long W = 0;
+  if (ok && m > 0) {
+    W = actg[g * words];
+    if (words > 1) W |= (unsigned long long)actg[g * words + 1] << 32;
+    if (m < 64) W &= (1ull << m) - 1ull;
+  }
+  W = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(W >> 32)) << 32) |
+      (unsigned)__builtin_amdgcn_readfirstlane((int)W);
+  // H padded with the identity, Q zero
+  for (int e = lane; e < WN * WN; e += 64) {
+    const int row = e >> 5, col = e & (WN - 1);
+    const bool in = row < n && col < n;
+    const double h = Hq[in ? row * n + col : 0];
+    Lm[row * WS + col] = in ? h : (row == col ? 1.0 : 0.0);
+    Qm[row * WS + col] = 0.0;
+  }
+  posb[lane] = -1.0;
+  if (lane < W_COL) colk[lane] = 0.0;
+  const bool var = lane < n;
+  double ui = var ? gxg[g * n + lane] : 0.0;  // the running g, u_k = (L^{-1} g)_k from step k on
+  double invLd = var ? 0.0 : 1.0;             // 1 / L[lane][lane] (1 on the padding)
+  wave_lds_sync();
+
+  // ---- H = L L^T (right-looking, in place) and u = L^{-1} g.  Step k updates
+  // the whole rows k+1.. of the symmetric trailing block, the two halves of
+  // the wave on alternate columns (the upper triangle is redundant and free:
+  // no predicate in the loop; the last trip of the upper half may touch the
+  // row's padding word, colk is zero there)
+  for (int k = 0; k < n; ++k) {
+    const double ik = rsq(Lm[k * WS + k]);
+    const double uk = readlane_d(ui, k) * ik;
+    const double lik = i >= k ? Lm[i * WS + k] * ik : 0.0;
+    wave_lds_sync();
+    if (half == 0) {
+      colk[i] = i > k ? lik : 0.0;
+      if (i >= k) Lm[i * WS + k] = lik;
+    }
+    if (lane == k) {
+      ui = uk;
+      invLd = ik;
+    } else if (low && lane > k) {
+      ui = __builtin_fma(-lik, uk, ui);
+    }
+    wave_lds_sync();
+    const double nl = i > k ? -lik : 0.0;
+    double *row = Lm + i * WS + k + 1 + half;
+    const double *col = colk + k + 1 + half;
+    const int trips = (WN - k) / 2;
+#pragma unroll 4
+    for (int jj = 0; jj < trips; ++jj) row[2 * jj] = __builtin_fma(nl, col[2 * jj], row[2 * jj]);
+    wave_lds_sync();
+  }
+  if (low) ub[lane] = ui;
+  wave_lds_sync();
+
+  // ---- D_W^T = Q R over the active rows in row order
+  // c_lane = q_lane . v and v -= sum_s c_s q_s over the rows so far (the q_s
+  // past them are zero); cl += c_lane
+  int cnt = 0;
+  auto project = [&](double &v, double &cl) {
+    wave_lds_sync();
+    if (low) vb[lane] = v;
+    wave_lds_sync();
+    if (low) {
+      double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+      for (int j = 0; j < WN; j += 2) {
+        c0 = __builtin_fma(Qm[lane * WS + j], vb[j], c0);
+        c1 = __builtin_fma(Qm[lane * WS + j + 1], vb[j + 1], c1);
+      }
+      const double c = c0 + c1;
+      cl += c;
+      cb[lane] = c;
+    }
+    wave_lds_sync();
+    if (low) {
+      for (int s0 = 0; s0 < cnt; s0 += 4) {
+#pragma unroll
+        for (int s = s0; s < s0 + 4; ++s) v = __builtin_fma(-cb[s], Qm[s * WS + lane], v);
+      }
+    }
+  };
+  for (unsigned long long rem = W; rem != 0; rem &= rem - 1ull) {
+    const int r = __builtin_ctzll(rem);
+    // row r of D: L d^T = a_r^T, component j at lane j (0 on the padding and the upper lanes)
+    double v = var ? Aq[r * n + lane] : 0.0;
+#pragma unroll
+    for (int k = 0; k < WN; ++k) {
+      const double dk = readlane_d(v * invLd, k);
+      const double lk = (low && lane > k) ? Lm[i * WS + k] : 0.0;
+      v = lane == k ? dk : __builtin_fma(-lk, dk, v);
+    }
+    const double dd = wave_sum(low ? v * v : 0.0);
+    double cl = 0.0;  // R[lane][cnt]
+    project(v, cl);
+    project(v, cl);
+    const double nd2 = wave_sum(low ? v * v : 0.0);
+    // (every lane holds the same sums; the readfirstlane tells the compiler so)
+    if (__builtin_amdgcn_readfirstlane((int)(cnt < WN && nd2 > kDepTol * dd))) {
+      const double rn = rsq(nd2);
+      wave_lds_sync();
+      if (low) Qm[cnt * WS + lane] = v * rn;
+      if (lane < cnt) Lm[lane * WS + cnt] = cl;  // R above L's diagonal
+      if (lane == 0) {
+        ir[cnt] = rn;
+        posb[r] = (double)cnt;
+      }
+      ++cnt;
+    }
+  }
+  wave_lds_sync();
+
+  // ---- z = -(u - Q Q^T u), R dlam = -Q^T u, L^T dx = z
+  double z = low ? ub[lane] : 0.0, cu = 0.0;
+  project(z, cu);
+  z = -z;
+  double y = -cu;  // the right-hand side, then dlam of position `lane`
+  const double invRd = lane < cnt ? ir[lane] : 0.0;
+  for (int t = cnt - 1; t >= 0; --t) {
+    const double yt = readlane_d(y * invRd, t);
+    if (lane == t) y = yt;
+    else if (lane < t) y = __builtin_fma(-Lm[lane * WS + t], yt, y);
+  }
+  double dx = z;
+#pragma unroll
+  for (int j = WN - 1; j >= 0; --j) {
+    const double dj = readlane_d(dx * invLd, j);
+    const double lj = lane < j ? Lm[j * WS + i] : 0.0;
+    dx = lane == j ? dj : __builtin_fma(-lj, dj, dx);
+  }
+  if (!ok || !var) dx = 0.0;
+
+  // ------------------------------------------------------------------ store
+  double *X = lds + W_X, *DX = lds + W_DX, *DL = lds + W_DL, *LM = lds + W_LM;
+  wave_lds_sync();
+  if (low) {
+    cb[lane] = lane < cnt ? y : 0.0;
+    X[lane] = (ok && var) ? xg[g * n + lane] : 0.0;
+    DX[lane] = dx;
+  }
+  wave_lds_sync();
+  {
+    // row `lane`: dlam through its position, lam where its bit is set
+    const int p = (int)posb[lane];
+    const double dl = p >= 0 ? cb[p] : 0.0;
+    const bool inW = (W >> lane) & 1ull;
+    DL[lane] = dl;
+    LM[lane] = inW ? lamg[g * m + lane] : 0.0;
+    if (gbg && lane < m) gbg[g * m + lane] = p >= 0 ? -dl : 0.0;
+  }
+  if (gfg && var) gfg[g * n + lane] = dx;
+  wave_lds_sync();
+  if (gHg) {
+    double *o = gHg + g * (long long)n * n;
+    for (int e = lane; e < n * n; e += 64) {
+      const int row = e / n, col = e - row * n;
+      o[e] = 0.5 * sym2(DX[row], X[col], X[row], DX[col]);
+    }
+  }
+  if (gAg && m > 0) {
+    double *o = gAg + g * (long long)m * n;
+    for (int e = lane; e < m * n; e += 64) {
+      const int row = e / n, col = e - row * n;
+      o[e] = sym2(DL[row], X[col], LM[row], DX[col]);
+    }
+  }
+}
+
+}  // namespace bwd
+}  // namespace qpb
+
+extern "C" hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, const double *A, const double *x,
+                                         const double *lam, const uint32_t *active, const int32_t *status,
+                                         const double *gx, double *gH, double *gf, double *gA, double *gb,
+                                         hipStream_t stream) {
+  if (d->n > 16 || d->m > 32) {  // one workgroup of one wave per QP
+    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x, lam,
+                       active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+#define QPB_BWD_LAUNCH(MR, N16)                                                                                 \
+  hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR, N16>), dim3((unsigned)blocks), dim3(64), 0, stream, H, A, x, \
+                     lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch)
+  const bool n16 = d->n == 16;
+  if (d->m <= 16) {
+    if (n16) QPB_BWD_LAUNCH(1, true);
+    else QPB_BWD_LAUNCH(1, false);
+  } else {
+    if (n16) QPB_BWD_LAUNCH(2, true);
+    else QPB_BWD_LAUNCH(2, false);
+  }
+#undef QPB_BWD_LAUNCH
+  return hipGetLastError();
+}

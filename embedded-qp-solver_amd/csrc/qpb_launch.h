@@ -32,6 +32,11 @@ typedef hipError_t qpb_gi_eq_launcher(const qpb_desc *d, int meq, const double *
                                       int32_t *iters, hipStream_t stream);
 QPB_LAUNCHER qpb_gi_eq_launcher qpb_launch_gi_eq,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_wave_eq;                         // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_backward: n <= 32, m <= 64 (qpb_kkt_bwd.hip); any of gH, gf, gA, gb may be NULL
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, const double *A, const double *x,
+                                           const double *lam, const uint32_t *active, const int32_t *status,
+                                           const double *gx, double *gH, double *gf, double *gA, double *gb,
+                                           hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

@@ -88,6 +88,24 @@ static_assert(route_eq(33, 0).step == 0 && route_eq(32, 65).step == 0 && route_e
 static_assert(route_eq(kEqMaxN, kEqMaxM).step > 0 && route_eq(kEqMaxN + 1, 1).step == 0 &&
               route_eq(1, kEqMaxM + 1).step == 0);
 
+// qpb_solve_backward: the two wavefront-level classes of qpb_kkt_bwd.hip,
+// named by the forward kernel whose lane mapping they share; above them there
+// is no backward kernel yet: step 0, and the call is unsupported.
+constexpr Route route_bwd(int n, int m) {
+  if (n <= 16 && m <= 32) return {Kernel::gi_dense, step_of(Kernel::gi_dense)};
+  if (n <= 32 && m <= 64) return {Kernel::gi_wave, step_of(Kernel::gi_wave)};
+  return {Kernel::gi_gram, 0};
+}
+constexpr int kBwdMaxN = 32, kBwdMaxM = 64;  // the limit route_bwd's step 0 stands for
+
+static_assert(route_bwd(16, 32).kernel == Kernel::gi_dense && route_bwd(1, 0).kernel == Kernel::gi_dense);
+static_assert(route_bwd(16, 33).kernel == Kernel::gi_wave && route_bwd(17, 0).kernel == Kernel::gi_wave);
+static_assert(route_bwd(32, 64).kernel == Kernel::gi_wave && route_bwd(32, 64).step == 1LL << 25);
+static_assert(route_bwd(16, 32).step == 1LL << 27);
+static_assert(route_bwd(33, 0).step == 0 && route_bwd(32, 65).step == 0 && route_bwd(128, 256).step == 0);
+static_assert(route_bwd(kBwdMaxN, kBwdMaxM).step > 0 && route_bwd(kBwdMaxN + 1, 1).step == 0 &&
+              route_bwd(1, kBwdMaxM + 1).step == 0);
+
 // One array of a batched call: per_qp elements per QP from base.  Only an
 // optional array may be NULL, and then it is NULL in every chunk.
 template <class T>

@@ -12,6 +12,7 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve(H, f, A, b)          -> qpb_solve       (active set, m > 0)
     solve(H, f)                -> qpb_solve, m=0  (test/qp_ref.py:35 semantics)
     solve_eq(H, f, A, b, meq)  -> qpb_solve_eq    (rows 0 .. meq-1 of A are equalities)
+    solve_backward(H, A, sol, gx) -> qpb_solve_backward (gradients of a solve; autograd: qpb.diff)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
     ref_generate(n, B, seed)   -> qpb_ref_generate (the reference generator, bit for bit)
@@ -69,6 +70,10 @@ _lib.qpb_solve_eq.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
 _lib.qpb_solve_eq.restype = ctypes.c_int
 _lib.qpb_solve_eq_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 9
 _lib.qpb_solve_eq_host.restype = ctypes.c_int
+_lib.qpb_solve_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 12
+_lib.qpb_solve_backward.restype = ctypes.c_int
+_lib.qpb_solve_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
+_lib.qpb_solve_backward_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
 _lib.qpb_ref_solve.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 6
@@ -263,6 +268,82 @@ def _solve_host(meq, H, f, A, b, max_iter, feas_tol) -> Solution:
         rc = _lib.qpb_solve_eq_host(ctypes.byref(d), meq, p(H), p(f), p(A), p(b), p(x), p(lam), p(act), p(st), p(it))
         _check(rc, "qpb_solve_eq_host")
     return Solution(x, lam, act, st, it)
+
+
+NEED_ALL = ("H", "f", "A", "b")
+
+
+def _need_set(need) -> set:
+    need = set(need)
+    if not need or not need <= set(NEED_ALL):
+        raise ValueError(f"need must be a non-empty subset of {NEED_ALL}")
+    return need
+
+
+def solve_backward(H, A, sol: Solution, gx, *, need=NEED_ALL, stream=None):
+    """Gradients of a solve through its KKT system (qpb_solve_backward): given
+    ``sol`` from ``solve`` / ``solve_eq`` on (H, f, A, b) and the cotangent
+    ``gx = dl/dx`` (B, n), returns ``(gH, gf, gA, gb)`` = dl/dH (B,n,n), dl/df
+    (B,n), dl/dA (B,m,n), dl/db (B,m) at fixed active set (qpb.h has the
+    contract).  Entries left out of ``need`` come back as None and are neither
+    computed nor stored; with A None (m = 0) gA and gb are None.  ``sol.status``
+    may be None: every QP then counts as OK.  QPs whose status is not OK get
+    zeros.  n <= 32 and m <= 64; torch CUDA float64 tensors as for ``solve``.
+    """
+    import torch
+    B, n, m = _solve_shape("qpb.solve_backward", H, gx, A, None if A is None else sol.lam)
+    need = _need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if m and (not sol.active.is_contiguous() or sol.active.shape != (B, (m + 31) // 32)
+              or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(m/32)) tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(B, n, n) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    gA = new(B, m, n) if m and "A" in need else None
+    gb = new(B, m) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None  # m == 0 and only A / b wanted
+    d = Desc(n, m, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_backward(ctypes.byref(d), _ptr(H), _ptr(A) if m else None, _ptr(sol.x),
+                                 _ptr(sol.lam) if m else None, _ptr(sol.active) if m else None, _ptr(sol.status),
+                                 _ptr(gx), _ptr(gH), _ptr(gf), _ptr(gA), _ptr(gb), _stream_ptr(stream))
+    _check(rc, "qpb_solve_backward")
+    return gH, gf, gA, gb
+
+
+def solve_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
+    """numpy in / numpy out (qpb_solve_backward_host): ``solve_backward`` with host arrays."""
+    import numpy as np
+    need = _need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    m = 0 if A is None else A.shape[1]
+    lam = act = None
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        lam = np.ascontiguousarray(sol.lam, dtype=np.float64)
+        act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros((B, n, n)) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    gA = np.zeros((B, m, n)) if m and "A" in need else None
+    gb = np.zeros((B, m)) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None
+    d = Desc(n, m, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_backward_host(ctypes.byref(d), p(H), p(A), p(x), p(lam), p(act), p(st), p(gx), p(gH), p(gf),
+                                      p(gA), p(gb))
+    _check(rc, "qpb_solve_backward_host")
+    return gH, gf, gA, gb
 
 
 def active_mask_to_bool(active, m: int):

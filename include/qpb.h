@@ -12,6 +12,7 @@
  *   test/qp_ref.py:35  solve_qp(P, q, G=0, h=0)          qpb_solve(m = 0)
  *   north_star active-set over (H, f, A, b)              qpb_solve(m > 0)
  *   ... with equality rows, solve_qp(P, q, G, h, A, b)    qpb_solve_eq
+ *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -126,7 +127,7 @@ extern "C" {
 
 /* qpb_version() reports "qpb MAJOR.MINOR (...)" */
 #define QPB_VERSION_MAJOR 0
-#define QPB_VERSION_MINOR 13
+#define QPB_VERSION_MINOR 14
 
 /* limits of this build's kernels: n <= 16, m <= 32 one QP per 16-lane DPP
  * row (qpb_gi.hip); n <= 32, m <= 64 one QP per wavefront (qpb_gi_wave.hip);
@@ -230,6 +231,64 @@ int qpb_solve_eq_host(const qpb_desc *desc, int32_t meq, const double *H,
 		      const double *f, const double *A, const double *b,
 		      double *x, double *lam, uint32_t *active, int32_t *status,
 		      int32_t *iters);
+
+/* The backward pass of qpb_solve / qpb_solve_eq: the vector-Jacobian product
+ * of x*(H, f, A, b).  Given a solve's x, lam, active and status and the
+ * cotangent gx = dl/dx (n per QP), one KKT solve per QP at FIXED active set:
+ * W = the rows whose bit is set in `active`, A_W their rows,
+ *
+ *     [ H    A_W^T ] [ dx   ]     [ gx ]
+ *     [ A_W   0    ] [ dlam ] = - [ 0  ]
+ *
+ *     gf = dx                             (n per QP)
+ *     gH = 1/2 (dx x^T + x dx^T)          (n x n; symmetric bit for bit, as
+ *                                          the H this header requires)
+ *     gA_i = dlam_i x^T + lam_i dx^T      (m x n; row i in W, 0 otherwise)
+ *     gb_i = -dlam_i                      (m;     row i in W, 0 otherwise)
+ *
+ * An equality row of qpb_solve_eq is simply a row whose bit is set and whose
+ * multiplier may have either sign.  H is factored and the rows of
+ * A_W L^{-T} are orthogonalised in row order; the Schur complement is never
+ * formed.  This is the derivative at fixed active set:
+ *   weakly active   a row with its bit set and lam_i = 0 counts as active, so
+ *                   the result is one of the two one-sided derivatives.
+ *   left-out row    a dependent equality the forward solve left out has its
+ *                   bit clear and gets zero gradients.
+ *   dependent row   the forward solve never marks one, a caller's own mask
+ *                   can: a row whose part orthogonal to the set rows before it
+ *                   has |d2|^2 <= 1e-24 |d|^2 (the kernels' test) is skipped,
+ *                   dlam_i = 0: gb_i = 0 and gA_i = lam_i dx^T.
+ * desc is the forward call's: n, m and batch are used, max_iter and feas_tol
+ * are ignored, flags must be 0.  Layouts are the forward's.
+ *   required        H, x and gx; with m > 0 also A, lam and active.
+ *   status          may be NULL: every QP then counts as QPB_OK.
+ *   gH, gf, gA, gb  each may be NULL: that gradient is neither computed nor
+ *                   stored; at least one must be given.  With m == 0, gA and
+ *                   gb are ignored.
+ * Every element of every non-NULL output of every QP is written, and nothing
+ * else; a QP whose status is not QPB_OK gets zeros in all of them; a QP's
+ * outputs depend on its own inputs only.
+ * Errors, in order: the descriptor as qpb_solve; flags != 0
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64 QPB_ERR_UNSUPPORTED; batch == 0
+ * returns 0 before the pointers are looked at; missing pointers
+ * QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits: n <= 16, m <= 32 runs four QPs per wavefront, the rest of n <= 32,
+ * m <= 64 one QP per wavefront (qpb_kkt_bwd.hip).  The n <= 128 class needs a
+ * workgroup-level kernel, and the backward of qpb_solve_box (gradients for lb
+ * and ub, the active rows as unit vectors) is not there either: follow-ups.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_backward(const qpb_desc *desc, const double *H, const double *A,
+		       const double *x, const double *lam,
+		       const uint32_t *active, const int32_t *status,
+		       const double *gx, double *gH, double *gf, double *gA,
+		       double *gb, void *stream);
+
+/* Same with host pointers, as qpb_solve_host. */
+int qpb_solve_backward_host(const qpb_desc *desc, const double *H,
+			    const double *A, const double *x,
+			    const double *lam, const uint32_t *active,
+			    const int32_t *status, const double *gx, double *gH,
+			    double *gf, double *gA, double *gb);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
