@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <type_traits>
 #include <utility>
 
 // Cached per-(device, stream) device scratch (qpb_workspace.hip): `launch`
@@ -268,6 +269,16 @@ __device__ __forceinline__ int wave_max4(int v) {
   const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
   const int ab = a > b ? a : b, cd = c > d ? c : d;
   return ab > cd ? ab : cd;
+}
+
+// A T at byte offset `off` (per lane, 32 bits) from a wave-uniform base: the
+// access takes the base from an SGPR pair and the offset from one VGPR
+// (global_load/store v, v_off, s[base:base+1]) -- no 64-bit address per lane.
+template <class T, class B>
+__device__ __forceinline__ auto &at_off(B *base, uint32_t off) {
+  using P = std::conditional_t<std::is_const_v<B>, const char, char>;
+  using R = std::conditional_t<std::is_const_v<B>, const T, T>;
+  return *reinterpret_cast<R *>(reinterpret_cast<P *>(base) + off);
 }
 
 // Diagnostic builds only (STAMP = true, qpb_solve_sections): s_memrealtime stamps

@@ -126,9 +126,14 @@ __device__ __forceinline__ void gi_group(
   // the batch's last QP -- same trip count, so they never extend the wave's
   // loop -- and store nothing.  Every lane of the wave stays live, so the
   // cross-row reads (wave_max4's readlanes) only ever see real QP state.
-  const long long graw = grp * QPB + slot;
-  const bool live = graw < batch;
-  const long long g = live ? graw : batch - 1;
+  // The group's first QP, g0 = 4 grp, is wave-uniform and so is every base
+  // address below; a lane adds a 32-bit byte offset inside the group's block
+  // (under 16 KiB: 4 QPs of m <= 32 rows of n <= 16 doubles).  `rem` QPs of the
+  // group exist (batch - 1 >= g0, so a replaying row's index rem - 1 is in 0..3).
+  const long long g0 = grp * QPB;
+  const int rem = (int)__builtin_elementwise_min(batch - g0, (long long)QPB);
+  const bool live = slot < rem;
+  const uint32_t sl = (uint32_t)(live ? slot : rem - 1);  // this row's QP inside the group
   if constexpr (FULL) {
     n = NL;
     m = NL * MR;
@@ -150,11 +155,14 @@ __device__ __forceinline__ void gi_group(
   // (flags & QPB_FLAG_DIAG_L2: every QP reads the inputs of QP g mod 512;
   // QPB_FLAG_DIAG_MALL: of QP g mod 16384 (107 MB, Infinity-Cache resident
   // after the first launch) -- diagnostics that take HBM out of the kernel time)
-  const long long gi = (flags & QPB_FLAG_DIAG_L2) ? (g & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (g & 16383) : g;
-  const double *Hq = Hg + gi * (long long)n * n;
+  // (512 and 16384 are multiples of 4: the group's four indices never wrap,
+  // the masked index of its first QP serves all of them)
+  const long long gi0 = (flags & QPB_FLAG_DIAG_L2) ? (g0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (g0 & 16383) : g0;
+  const double *Hs = Hg + gi0 * (long long)n * n;
   // m == 0: A/b may be NULL -- point the (masked) row loads at H instead
-  const double *Aq = m > 0 ? Ag + gi * (long long)m * n : Hq;
-  const double *bq = m > 0 ? bg + gi * (long long)m : Hq;
+  const double *As = m > 0 ? Ag + gi0 * (long long)m * n : Hs;
+  const double *bs = m > 0 ? bg + gi0 * (long long)m : Hs;
+  const uint32_t un = (uint32_t)n, umn = (uint32_t)m * un;
   double Lr[NL];  // row l of H, becomes row l of L
   double E[MR][NL];
   double s[MR], bl[MR], thr[MR];
@@ -165,8 +173,9 @@ __device__ __forceinline__ void gi_group(
   // b and f with the matrices (same round trip)
   double bv[MR];
 #pragma unroll
-  for (int r = 0; r < MR; ++r) bv[r] = bq[(FULL || l + NL * r < m) ? l + NL * r : 0];
-  const double fv = fg[gi * n + (l < n ? l : n - 1)];
+  for (int r = 0; r < MR; ++r)
+    bv[r] = at_off<double>(bs, (sl * (uint32_t)m + (uint32_t)((FULL || l + NL * r < m) ? l + NL * r : 0)) * 8u);
+  const double fv = at_off<double>(fg + gi0 * n, (sl * un + (uint32_t)(l < n ? l : n - 1)) * 8u);
   const double fl = (N16 || l < n) ? fv : 0.0;
   [[maybe_unused]] const int hr = l >> 3, hc = 2 * (l & 7);
   // stage 16 rows of a 16-column matrix (as loaded) in this QP's slot (L and
@@ -209,17 +218,20 @@ __device__ __forceinline__ void gi_group(
     // each of the wave's 4 QPs -- lane l gets row 2t + (l>>3), columns
     // 2(l&7), 2(l&7)+1.  Rows reach their owner lane through a transpose in
     // this QP's LDS slot (free until the factorisation ends).
+    const uint32_t hoff = (uint32_t)(hr * NL + hc) * 8u;  // row hr, column hc of a 16-column matrix
+    const double *Hl = &at_off<double>(Hs, sl * (NL * NL * 8u) + hoff);
+    const double *Al = &at_off<double>(As, sl * umn * 8u + hoff);
     double2 hv[8];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) hv[t] = *reinterpret_cast<const double2 *>(&Hq[(2 * t + hr) * NL + hc]);
+    for (int t = 0; t < 8; ++t) hv[t] = *reinterpret_cast<const double2 *>(&Hl[2 * t * NL]);
     auto load_a = [&](int r, double2 (&v)[8]) {
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const int row = NL * r + 2 * t + hr;
         if constexpr (FULL)
-          v[t] = *reinterpret_cast<const double2 *>(&Aq[row * NL + hc]);
+          v[t] = *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]);
         else
-          v[t] = row < m ? *reinterpret_cast<const double2 *>(&Aq[row * NL + hc]) : make_double2(0.0, 0.0);
+          v[t] = row < m ? *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]) : make_double2(0.0, 0.0);
       }
     };
     // all input rows in flight at once (one HBM round trip); instruction
@@ -248,9 +260,10 @@ __device__ __forceinline__ void gi_group(
     wave_lds_sync();
   } else {  // padded n < 16: clamped per-lane row loads, identity outside n
     const int lc = l < n ? l : n - 1;
+    const uint32_t hrow = (sl * un + (uint32_t)lc) * un * 8u;  // the lane's row of H
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
-      const double h = Hq[lc * n + (j < n ? j : n - 1)];
+      const double h = at_off<double>(Hs, hrow + (uint32_t)(j < n ? j : n - 1) * 8u);
       Lr[j] = (l < n && j < n) ? h : (l == j ? 1.0 : 0.0);
     }
 #pragma unroll
@@ -258,9 +271,10 @@ __device__ __forceinline__ void gi_group(
       const int row = l + NL * r;
       const bool ok = row < m;
       const int rc = ok ? row : 0;
+      const uint32_t arow_off = (sl * umn + (uint32_t)rc * un) * 8u;
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
-        const double a = Aq[rc * n + (j < n ? j : n - 1)];
+        const double a = at_off<double>(As, arow_off + (uint32_t)(j < n ? j : n - 1) * 8u);
         E[r][j] = (ok && j < n) ? a : 0.0;
       }
       row_norms(r, E[r]);
@@ -703,13 +717,20 @@ __device__ __forceinline__ void gi_group(
   // ------------------------------------------------------------- outputs
   // (the active rows of A re-read, one coalesced 128-B row per active position)
   const int qm = __builtin_elementwise_min(wave_max4(q), NL);
-  // The QP index and its A block again, recomputed from an opaque copy of the
-  // slot instead of held across the loop (held, the allocator spilled them)
+  // The group's scalar bases and the lane's QP inside the group again,
+  // recomputed from opaque copies of the group index and the slot instead of
+  // held across the loop (held, the allocator spilled them)
   int slot_o = slot;
   asm volatile("" : "+v"(slot_o));
-  const long long go = live ? grp * QPB + slot_o : batch - 1;
-  const long long gio = (flags & QPB_FLAG_DIAG_L2) ? (go & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (go & 16383) : go;
-  const double *Aqo = m > 0 ? Ag + gio * (long long)m * n : Hg + gio * (long long)n * n;
+  long long grp_o = grp;
+  asm volatile("" : "+s"(grp_o));
+  const long long go0 = grp_o * QPB;
+  const int rem_o = (int)__builtin_elementwise_min(batch - go0, (long long)QPB);
+  const bool live_o = slot_o < rem_o;
+  const uint32_t slo = (uint32_t)(live_o ? slot_o : rem_o - 1);
+  const long long gio0 =
+      (flags & QPB_FLAG_DIAG_L2) ? (go0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (go0 & 16383) : go0;
+  const double *Aso = m > 0 ? Ag + gio0 * (long long)m * n : Hg + gio0 * (long long)n * n;
   // The A-row loads go out first, in at most two groups of eight (one
   // wave-uniform test per group: a test per load made each load a branch
   // with its own wait); the work that does not need them -- the multipliers by
@@ -717,13 +738,13 @@ __device__ __forceinline__ void gi_group(
   // in flight.  Positions past qm read a valid row and are not summed.
   // Addresses: the byte offset of the position's row (m <= 32 rows of n <= 16
   // doubles: below 4 KiB) is formed once per lane, before the broadcast, and
-  // each load adds the broadcast offset to this lane's column base -- a DPP
-  // move and one 64-bit add per load instead of a multiply, a sign extension
-  // and a shifted add behind every broadcast.
+  // each load adds the broadcast offset to this lane's 32-bit column offset
+  // inside the group's A block -- a DPP move and one 32-bit add per load on the
+  // group's scalar base.
   const uint32_t iob = (uint32_t)(iam > 0 ? iam : 0) * (uint32_t)n * 8u;
   asm volatile("s_nop 1" ::"v"(iob));  // its DPP reads below may sit behind a branch only
   const int lc = l < n ? l : n - 1;
-  const char *Acol = reinterpret_cast<const char *>(Aqo + lc);
+  const uint32_t acol = (slo * (uint32_t)m * (uint32_t)n + (uint32_t)lc) * 8u;
   double arow[NL];
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
@@ -731,7 +752,7 @@ __device__ __forceinline__ void gi_group(
       __builtin_amdgcn_sched_barrier(0);
       unroll<8>([&](auto K) {
         constexpr int kk = k0 + K;
-        arow[kk] = *reinterpret_cast<const double *>(Acol + (uint32_t)bci<kk>((int)iob));
+        arow[kk] = at_off<double>(Aso, acol + (uint32_t)bci<kk>((int)iob));
       });
     }
   });
@@ -753,7 +774,8 @@ __device__ __forceinline__ void gi_group(
 #pragma unroll
   for (int r = 0; r < MR; ++r) {
     const int row = l + NL * r;
-    if (live && (FULL || row < m)) lamg[go * m + row] = lamr[r];
+    if (live_o && (FULL || row < m))
+      at_off<double>(lamg + go0 * m, (slo * (uint32_t)m + (uint32_t)row) * 8u) = lamr[r];
   }
   uint32_t w0 = 0;
 #pragma unroll
@@ -761,7 +783,7 @@ __device__ __forceinline__ void gi_group(
     const unsigned long long bal = __ballot(act[r]);
     w0 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
   }
-  if (live && l == 0 && m > 0) actg[go] = w0;
+  if (live_o && l == 0 && m > 0) at_off<uint32_t>(actg + go0, slo * 4u) = w0;
   // x = -H^{-1} (f + A^T lam): g = f + sum_k u_k a_{iam_k}, then L y = g,
   // L^T x = -y, lane-parallel: step k broadcasts the finished component from
   // lane k; finished lanes keep updating (dead values) and the components are
@@ -803,10 +825,10 @@ __device__ __forceinline__ void gi_group(
     const double bad = row_min((__builtin_fabs(xl) < kInf) ? 0.0 : -1.0);
     if (status == QPB_OK && bad < 0.0) status = QPB_NUMERICAL;
   }
-  if (live && (N16 || l < n)) xg[go * n + l] = xl;
-  if (live && l == 0) {
-    statg[go] = status;
-    if (itg) itg[go] = it;
+  if (live_o && (N16 || l < n)) at_off<double>(xg + go0 * n, (slo * (uint32_t)n + (uint32_t)l) * 8u) = xl;
+  if (live_o && l == 0) {
+    at_off<int32_t>(statg + go0, slo * 4u) = status;
+    if (itg) at_off<int32_t>(itg + go0, slo * 4u) = it;
   }
   clk.tick(11);
   clk.flush(dbg);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Where the n <= 16 active-set kernel's instructions execute: basic block x
 opcode class x executions per wave, for one instantiation of gi_dense_kernel.
-Runs on the CPU.
+Runs on the CPU.  Beside the issue classes, every section has a row ADDR64 (64-bit
+address arithmetic on the VALU) and READLANE (v_readlane / v_readfirstlane).
 
   static counts   a hipcc -S listing of csrc/qpb_gi.hip (the Makefile's flags
                   plus -gline-tables-only, which leaves the code as it is): the
@@ -203,6 +204,13 @@ def op_class(op, text):
             c["DPP"] = 1
         if op.startswith("v_cndmask"):
             c["CNDMASK"] = 1
+        # 64-bit address arithmetic on the VALU: shifted adds, carry pairs, the sign
+        # extension in front of them
+        if op.startswith(("v_lshl_add_u64", "v_add_co_u32", "v_addc_co_u32", "v_ashrrev_i32", "v_ashrrev_i64",
+                          "v_lshlrev_b64", "v_mad_u64_u32", "v_mad_i64_i32")):
+            c["ADDR64"] = 1
+        if op.startswith(("v_readlane", "v_readfirstlane")):
+            c["READLANE"] = 1
     elif op.startswith("s_"):
         c["SALU"] = 1
     elif op.startswith("ds_"):
