@@ -513,4 +513,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.0: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above)"; }

@@ -17,6 +17,11 @@
 //
 //     z = -(u - Q Q^T u),   dx = L^{-T} z,   R dlam = -Q^T u.
 //
+// u is projected in two passes, z -= Q (Q^T z) twice with Q^T u the sum of the
+// two coefficient vectors: the rounding of one pass, eps |u| inside span(Q),
+// reaches dx through L^{-T} as eps cond(H) |g|, and A_W dx = 0 is lost at
+// cond(H) = 1e10 when |W| is n or n - 1 (tests/test_bwd_cases.py).
+//
 // A row whose part orthogonal to the rows before it has |d2|^2 <= kDepTol |d|^2
 // (the forward's dependency test) is skipped: dlam_i = 0, it keeps only the
 // lam_i dx^T term of dl/dA_i.  The forward solve never produces such a mask.
@@ -154,6 +159,11 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   // the DPP-fused FMAs; the sched_barrier and the rsq chain keep every write
   // of Lr[j] and of the running g (previous step) well over two instructions
   // before these reads.  u_k = g_k / L_kk is final at step k, on lane k.
+  // D's update takes a_jk from lane j (column k of ITS row, the entry that
+  // becomes L_jk), not a_kj from the pivot row: the two triangles of the
+  // trailing block agree to eps |H| only, which next to a pivot of 1e-10 |H| is
+  // another L -- and D from one L with u and dx from the other broke both
+  // certificates at cond(H) = 1e10 (1e-9 where the wave kernel has 1e-15).
   double ya = var ? gv : 0.0, ul = 0.0, invLd = 0.0;
   unroll<NL>([&](auto K) {
     constexpr int k = K;
@@ -178,7 +188,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     unroll<NL - 1 - k>([&](auto J) {
       constexpr int j = k + 1 + J;
 #pragma unroll
-      for (int r = 0; r < MR; ++r) fmac_bc<k>(E[r][j], Lr[j], ne2[r]);
+      for (int r = 0; r < MR; ++r) fmac_bc<j>(E[r][j], Lr[k], ne2[r]);  // a_jk of lane j: L's own entry
       fmac_bc<k>(Lr[j], Lr[j], nc);
     });
     fmac_bc<k>(ya, ya, nc);  // lane k's own g_k becomes 0 (dead)
@@ -268,7 +278,11 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
 
   // ---- z = -(u - Q Q^T u), R dlam = -Q^T u
   const int qmax = wave_max4(cnt);
+  // (u is projected twice as the rows are: one pass leaves eps |u| of it in the
+  // span of Q, which L^{-T} magnifies by up to sqrt(cond H) -- all there is of
+  // dx when W leaves little or no freedom; cu sums the two passes' Q^T z)
   double z = ul, cu = 0.0;
+  project(z, cu, qmax);
   project(z, cu, qmax);
   z = -z;
   double y;  // dlam of position l
@@ -550,7 +564,9 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   wave_lds_sync();
 
   // ---- z = -(u - Q Q^T u), R dlam = -Q^T u, L^T dx = z
+  // (two passes, as in the dense kernel)
   double z = low ? ub[lane] : 0.0, cu = 0.0;
+  project(z, cu);
   project(z, cu);
   z = -z;
   double y = -cu;  // the right-hand side, then dlam of position `lane`

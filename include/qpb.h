@@ -257,7 +257,11 @@ int qpb_solve_eq_host(const qpb_desc *desc, int32_t meq, const double *H,
  *   dependent row   the forward solve never marks one, a caller's own mask
  *                   can: a row whose part orthogonal to the set rows before it
  *                   has |d2|^2 <= 1e-24 |d|^2 (the kernels' test) is skipped,
- *                   dlam_i = 0: gb_i = 0 and gA_i = lam_i dx^T.
+ *                   dlam_i = 0: gb_i = 0 and gA_i = lam_i dx^T.  At most n rows
+ *                   count; with more than n bits set the rows met after
+ *                   them, in row order, are skipped in the same way.
+ *   bits >= m       bits at positions >= m in the last word of `active` are
+ *                   ignored.
  * desc is the forward call's: n, m and batch are used, max_iter and feas_tol
  * are ignored, flags must be 0.  Layouts are the forward's.
  *   required        H, x and gx; with m > 0 also A, lam and active.

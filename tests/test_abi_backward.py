@@ -111,7 +111,7 @@ def test_version_names_the_backward_kernels():
     lib = _lib()
     lib.qpb_version.restype = ctypes.c_char_p
     v = lib.qpb_version().decode()
-    assert v.startswith("qpb 0.14 ") and "kkt_bwd v1.0" in v
+    assert v.startswith("qpb 0.14 ") and "kkt_bwd v1.1" in v
     assert "gi_eq v1.0" in v and "gi_dense v11.6" in v
 
 

@@ -11,38 +11,31 @@ max|delta| / (1 + max|ref|) per QP, and the certificate of the outputs (the two
 relative residuals of the backward system) <= KKT_TOL = 1e-9.  For scale: two
 fp64 algorithms on the CPU agree to 4e-13, with a certificate of 3e-14.
 
-Every call here goes through the C-ABI into buffers of the test's own, filled
+Every call here goes through the C-ABI (tests/bwd_harness.py, shared with
+tests/test_gpu_backward_edges.py) into buffers of the test's own, filled
 with 0xA5 and fenced by guard words: each test also checks that every element
 was written and nothing outside.  "Bitwise" compares two launches on the same
 QP.  The batch of 67 leaves the four-per-wave kernel a ragged last wave.
 """
-import ctypes
-import math
-
 import numpy as np
 import pytest
 
-import eq_oracle as EO
 import kkt_oracle as KO
+from bwd_harness import KKT_TOL, NAMES, X_TOL
+from bwd_harness import backward as _backward, dev as _dev, rel as _rel, same as _same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-X_TOL = 1e-6
-KKT_TOL = 1e-9
 OK, MAX_ITER, NOT_SPD = 0, 1, 2
 B = 67
 SEED = 11
-GUARD = 64  # doubles on either side of an output
 
 # (n, m, meq)
 DENSE_SHAPES = [(1, 1, 0), (1, 2, 1), (3, 0, 0), (5, 9, 2), (16, 32, 0), (16, 32, 4), (16, 32, 16)]
 WAVE_SHAPES = [(16, 33, 0), (17, 34, 3), (20, 40, 4), (32, 64, 8), (32, 64, 32)]
 # one shape per load / store path: n < 16, n == 16, the wave kernel
 PATH_SHAPES = [(5, 9, 2), (16, 32, 4), (20, 40, 4)]
-NAMES = ("H", "f", "A", "b")
-
-FILL8 = np.frombuffer(bytes([0xA5] * 8), dtype=np.int64)[0]
 
 
 @pytest.fixture(scope="module")
@@ -53,10 +46,6 @@ def qpb():
     return q
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _forward(qpb, H, f, A, b, meq, **kw):
     """solve_eq (solve at m = 0) on the GPU; numpy (x, lam, active words, status)."""
     if A.shape[1] == 0:
@@ -65,51 +54,6 @@ def _forward(qpb, H, f, A, b, meq, **kw):
         sol = qpb.solve_eq(_dev(H), _dev(f), _dev(A), _dev(b), meq, **kw)
     torch.cuda.synchronize()
     return sol.x.cpu().numpy(), sol.lam.cpu().numpy(), sol.active.cpu().numpy(), sol.status.cpu().numpy()
-
-
-def _shapes(Bq, n, m):
-    return {"H": (Bq, n, n), "f": (Bq, n), "A": (Bq, m, n), "b": (Bq, m)}
-
-
-def _backward(qpb, H, A, x, lam, act, st, g, need=NAMES, stream=None):
-    """qpb_solve_backward through the C-ABI on numpy inputs (st None: status
-    NULL).  Outputs live between guard words in buffers filled with 0xA5: every
-    element must have been written and no guard touched.  Returns a dict of the
-    numpy arrays in `need` (at m == 0 without A and b)."""
-    Bq, n = g.shape
-    m = A.shape[1]
-    ins = [_dev(H), _dev(A) if m else None, _dev(x), _dev(lam) if m else None, _dev(act) if m else None,
-           _dev(st) if st is not None else None, _dev(g)]
-    bufs, views = {}, {}
-    for k, shape in _shapes(Bq, n, m).items():
-        if k in need and math.prod(shape) > 0:
-            t = torch.empty(math.prod(shape) + 2 * GUARD, dtype=torch.float64, device="cuda")
-            t.view(torch.uint8).fill_(0xA5)
-            bufs[k], views[k] = t, t[GUARD:GUARD + math.prod(shape)].view(shape)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    d = qpb.Desc(n, m, Bq, 0, 0, 0.0)
-    s = stream if stream is not None else torch.cuda.current_stream()
-    rc = qpb.lib().qpb_solve_backward(ctypes.byref(d), *[ptr(t) for t in ins], *[ptr(views.get(k)) for k in NAMES],
-                                      ctypes.c_void_p(s.cuda_stream))
-    assert rc == 0, qpb.lib().qpb_last_error()
-    s.synchronize()
-    out = {}
-    for k, t in bufs.items():
-        raw = t.cpu().numpy().view(np.int64)
-        assert (raw[:GUARD] == FILL8).all() and (raw[-GUARD:] == FILL8).all(), (k, "guard words written")
-        assert not (raw[GUARD:-GUARD] == FILL8).any(), (k, "elements never written")
-        out[k] = views[k].cpu().numpy()
-    return out
-
-
-def _same(a, b):
-    return a.keys() == b.keys() and all(np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)) for k in a)
-
-
-def _rel(a, ref):
-    """max|delta| / (1 + max|ref|) per QP."""
-    ax = tuple(range(1, a.ndim))
-    return np.abs(a - ref).max(axis=ax) / (1.0 + np.abs(ref).max(axis=ax))
 
 
 _CASES = {}
