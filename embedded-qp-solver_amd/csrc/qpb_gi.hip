@@ -51,35 +51,11 @@
 // no LDS round trip, no copy of the vector in every lane.
 // No branch or select compares the lane id with a compile-time constant:
 // such masks are hoisted by the compiler and end up spilled (SGPR pressure).
-#include "qpb_common.h"
 #include "qpb_launch.h"  // with qpb.h
+#include "qpb_row16.h"   // the QP's LDS slot and the steps shared with gi_box and kkt_bwd
 
 namespace qpb {
-
-constexpr int NL = 16;  // lanes per QP
-constexpr int QPB = 4;  // QPs per workgroup (one wavefront)
-constexpr int RS = 18;  // row stride (doubles) of the input transposes: conflict-free b128
-
-// packed lower triangle of L (lrow).  Reads may run past a row's
-// end into the next rows (always inside the QP's slot): the solves never use
-// those values.
-constexpr int L_SIZE = lrow(NL);  // 136
-
-// LDS slot of one QP: 394 doubles = 3,152 B, 12,608 B per wave -> 12 waves
-// per CU (3 per SIMD, matching the VGPR budget).  A CU holds 12 one-wave
-// workgroups of up to 12,800 B of LDS each and 11 from 13,056 B
-// (tools/probe/occupancy_probe.hip, measured on the MI355X): the round-4 slot
-// (426 doubles, 13,632 B per wave) ran 11 waves per CU, one SIMD in four
-// with two (the wave timeline, tools/wave_timeline.py).
-constexpr int OFF_L = 0;                  // L (136)
-constexpr int OFF_T = L_SIZE;             // R, column-major 16 x 16: R[i][j] at j*16 + i;
-                                          // column 0 (no entry above the diagonal) doubles as
-                                          // the exchange row outside a DROP
-constexpr int OFF_XCH = OFF_T + NL * NL;  // 392: s_p, |d|^2 of the exchange
-constexpr int SLOT = OFF_XCH + 2;         // 394
-static_assert(SLOT % 2 == 0 && OFF_T % 2 == 0 && OFF_XCH % 2 == 0, "b128 alignment");
-static_assert(4 * SLOT * 8 <= kWaveLdsMax, "12 waves (3 per SIMD) per CU by LDS");
-static_assert(NL * RS <= SLOT, "input transposes are staged over the whole slot");
+using namespace row16;
 
 // out[r] = sum_j vec[lane j] * x[r][j] over the row's 16 lanes, DPP-fused;
 // the MR rows interleaved, two chains each (2 MR independent accumulators);
@@ -139,13 +115,9 @@ __device__ __forceinline__ void gi_group(
     m = NL * MR;
   }
 
-  // LDS slots in the order 0, 2, 1, 3: ds_read_b64 serves 32 lanes (two QPs)
-  // per cycle; slots 0/1 and 2/3 are 2 SLOT = 788 doubles apart, 40 banks mod
-  // 64, so contiguous 16-lane reads of the two QPs share 8 of the 64 banks
-  // (one slot apart they would share 20)
-  double *base = lds + (((slot & 1) << 1) | (slot >> 1)) * SLOT;
+  double *base = slot_base(lds, slot);
   double *Lp = base + OFF_L;
-  double *Tv = base + OFF_T;  // R, column-major (zero diagonal)
+  double *Tv = base + OFF_R;  // R, column-major (zero diagonal)
   // the exchange row in R's column 0: the back substitution never reads that
   // column, a DROP rebuilds it before use, an ADD at q = 0 rewrites it
   double *xch = Tv;
@@ -338,15 +310,7 @@ __device__ __forceinline__ void gi_group(
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < MR; ++r) s[r] = -ns[r];
-    // L -> LDS, packed rows (lane l writes row l), kept for the final solves.
-    // Lane l also writes its dead entries j > l, over the start of later rows:
-    // stores go in descending j, and a row's own entry at such an address has
-    // a smaller j, so it lands last (a wave's DS instructions execute in order).
-    unroll<NL>([&](auto J) {
-      constexpr int j = NL - 1 - J;
-      Lp[lrow(l) + j] = Lr[j];
-      wave_lds_sync();
-    });
+    store_l(Lp, l, Lr);  // kept for the final solves
   }
   // |D[r,:]|^2 = |a_r L^{-T}|^2: the loop's reflections are orthogonal, so it
   // never changes (the dependency test's scale).  Clamped to FLT_MAX instead
@@ -491,9 +455,7 @@ __device__ __forceinline__ void gi_group(
     // ---- r = R^{-1} d1: lane-parallel back substitution over the active positions
     double rm = 0.0;
     if (qmax > 0) {
-      // on the negated accumulator: nacc_l += R[l][j] * r_j, r_j = nacc_j * (-1/R_jj)
-      // read from lane j by the FMA itself (the product was written just
-      // before: fmac_bc_nop issues the DPP read hazard's wait states)
+      // on the negated accumulator (back_subst_step)
       const double ninv = -invRd;
       double nacc = (l < q) ? Dpl : 0.0;  // = -d1_l
       // steps 15 .. 1 in that order (column 0 holds no entry above the
@@ -501,10 +463,7 @@ __device__ __forceinline__ void gi_group(
       // tests are grouped 15..8, 7..4, 3..1 under one test per group: a flat
       // chain walked 12 to 14 failing tests per trip at the usual qmax of 2 or
       // 3 (one scalar compare and branch each), the groups walk 1 + 3.
-      auto step = [&](auto JC) {
-        constexpr int j = JC;
-        if (j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, Tv[j * NL + l]);
-      };
+      auto step = [&](auto JC) { back_subst_step<JC>(Tv, l, qmax, nacc, ninv); };
       if (qmax > 4) {
         if (qmax > 8) unroll<8>([&](auto JJ) { step(std::integral_constant<int, NL - 1 - JJ>{}); });
         unroll<4>([&](auto JJ) { step(std::integral_constant<int, 7 - JJ>{}); });
@@ -677,11 +636,7 @@ __device__ __forceinline__ void gi_group(
         if (j + 1 < qmax && j >= k && j < q - 1) {
           const double cj = bc<j>(gc), sj = bc<j>(gs);
 #pragma unroll
-          for (int r = 0; r < MR; ++r) {
-            const double e0 = E[r][j], e1 = E[r][j + 1];
-            E[r][j] = __builtin_fma(cj, e0, sj * e1);
-            E[r][j + 1] = __builtin_fma(-sj, e0, cj * e1);
-          }
+          for (int r = 0; r < MR; ++r) rotate_pair<j>(E[r], cj, sj);
         }
       });
       --q;
@@ -697,11 +652,7 @@ __device__ __forceinline__ void gi_group(
         });
         fn2[r] = a0 + a1;
       }
-      // back to the zero-diagonal form
-      wave_lds_sync();
-      const double dg = (l < q) ? Tv[l * NL + l] : 0.0;
-      wave_lds_sync();
-      if (l < q) Tv[l * NL + l] = 0.0;
+      const double dg = take_diagonal(Tv, l, q);
       invRd = (l < q) ? rcp1(dg) : 0.0;
       clk.tick(9);
     }
@@ -784,10 +735,7 @@ __device__ __forceinline__ void gi_group(
     w0 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
   }
   if (live_o && l == 0 && m > 0) at_off<uint32_t>(actg + go0, slo * 4u) = w0;
-  // x = -H^{-1} (f + A^T lam): g = f + sum_k u_k a_{iam_k}, then L y = g,
-  // L^T x = -y, lane-parallel: step k broadcasts the finished component from
-  // lane k; finished lanes keep updating (dead values) and the components are
-  // captured by same-address LDS stores.
+  // x = -H^{-1} (f + A^T lam): g = f + sum_k u_k a_{iam_k}, then the two solves
   double gl = fl;
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
@@ -798,33 +746,8 @@ __device__ __forceinline__ void gi_group(
       });
     }
   });
-  {
-    double acc = gl;
-    unroll<NL>([&](auto K) {
-      constexpr int kk = K;
-      const double yk = bc<kk>(acc * invd);
-      acc = __builtin_fma(-Lrow[kk], yk, acc);
-      xcap[kk] = yk;
-    });
-  }
-  wave_lds_sync();
-  {
-    double acc = xcap[l];
-    wave_lds_sync();
-    unroll<NL>([&](auto K) {
-      constexpr int kk = NL - 1 - K;
-      const double xk = bc<kk>(acc * invd);
-      acc = __builtin_fma(-Lp[lrow(kk) + l], xk, acc);
-      xcap[kk] = xk;
-    });
-  }
-  wave_lds_sync();
-  const double xl = -xcap[l];
-  {
-    // a non-finite x on any lane -> NUMERICAL for the QP
-    const double bad = row_min((__builtin_fabs(xl) < kInf) ? 0.0 : -1.0);
-    if (status == QPB_OK && bad < 0.0) status = QPB_NUMERICAL;
-  }
+  const double xl = solve_x(gl, invd, Lrow, Lp, l, xcap);
+  status = x_status(status, xl);
   if (live_o && (N16 || l < n)) at_off<double>(xg + go0 * n, (slo * (uint32_t)n + (uint32_t)l) * 8u) = xl;
   if (live_o && l == 0) {
     at_off<int32_t>(statg + go0, slo * 4u) = status;
@@ -894,21 +817,12 @@ extern "C" hipError_t qpb_launch_gi(const qpb_desc *d, const double *H, const do
                                     int32_t *status, int32_t *iters, hipStream_t stream) {
   const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
   const auto [max_iter, tol] = qpb_resolve_limits(d);
-#define QPB_GI_LAUNCH(MR, N16, FULL)                                                                               \
-  hipLaunchKernelGGL((qpb::gi_dense_kernel<MR, N16, FULL, false, 3>), dim3((unsigned)blocks), dim3(64), 0, stream, \
-                     H, f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol,    \
-                     d->flags)
-  const bool n16 = d->n == 16;
-  if (d->m <= 16) {
-    if (n16 && d->m == 16) QPB_GI_LAUNCH(1, true, true);
-    else if (n16) QPB_GI_LAUNCH(1, true, false);
-    else QPB_GI_LAUNCH(1, false, false);
-  } else {
-    if (n16 && d->m == 32) QPB_GI_LAUNCH(2, true, true);  // 3 waves per SIMD (VGPRs and LDS)
-    else if (n16) QPB_GI_LAUNCH(2, true, false);
-    else QPB_GI_LAUNCH(2, false, false);
-  }
-#undef QPB_GI_LAUNCH
+  // every form at 3 waves per SIMD (VGPRs and LDS)
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_kernel<MR(), N16(), FULL(), false, 3>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter,
+                       tol, d->flags);
+  });
   return hipGetLastError();
 }
 
@@ -918,21 +832,11 @@ extern "C" hipError_t qpb_launch_gi_eq(const qpb_desc *d, int meq, const double 
                                        int32_t *iters, hipStream_t stream) {
   const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
   const auto [max_iter, tol] = qpb_resolve_limits(d);
-#define QPB_GI_EQ_LAUNCH(MR, N16, FULL)                                                                          \
-  hipLaunchKernelGGL((qpb::gi_dense_eq_kernel<MR, N16, FULL, qpb::kEqOcc>), dim3((unsigned)blocks), dim3(64), \
-                     0, stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, meq, (long long)d->batch, \
-                     max_iter, tol)
-  const bool n16 = d->n == 16;
-  if (d->m <= 16) {
-    if (n16 && d->m == 16) QPB_GI_EQ_LAUNCH(1, true, true);
-    else if (n16) QPB_GI_EQ_LAUNCH(1, true, false);
-    else QPB_GI_EQ_LAUNCH(1, false, false);
-  } else {
-    if (n16 && d->m == 32) QPB_GI_EQ_LAUNCH(2, true, true);
-    else if (n16) QPB_GI_EQ_LAUNCH(2, true, false);
-    else QPB_GI_EQ_LAUNCH(2, false, false);
-  }
-#undef QPB_GI_EQ_LAUNCH
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_eq_kernel<MR(), N16(), FULL(), qpb::kEqOcc>), dim3((unsigned)blocks), dim3(64),
+                       0, stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, meq, (long long)d->batch,
+                       max_iter, tol);
+  });
   return hipGetLastError();
 }
 

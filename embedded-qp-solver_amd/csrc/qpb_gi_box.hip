@@ -20,26 +20,14 @@
 // 16 + l (lower bound); outputs use qpb_solve's m = 2n numbering (upper bounds
 // 0..n-1, lower bounds n..2n-1), i.e. A = [I; -I] row order.  Infinite bounds
 // (or a NULL lb / ub) are absent constraints: their slack is +inf.
-#include "qpb_common.h"
+// The QP's LDS slot (L | R, its column 0 the exchange row | s_p) and the steps
+// the kernel has in common with gi_dense are qpb_row16.h's.
 #include "qpb_launch.h"  // with qpb.h
+#include "qpb_row16.h"
 
 namespace qpb {
 namespace box {
-
-constexpr int NL = 16;  // lanes per QP
-constexpr int QPB = 4;  // QPs per wavefront
-constexpr int RS = 18;  // row stride of the H transpose (conflict-free b128 rows)
-constexpr int L_SIZE = lrow(NL);  // 136
-// per QP: L packed (136) | R column-major 16 x 16 with zero diagonal | exchange 32
-constexpr int OFF_L = 0;
-constexpr int OFF_R = L_SIZE;
-constexpr int OFF_XCH = OFF_R + NL * NL;
-constexpr int SLOT = OFF_XCH + 2;  // 394 doubles: s_p (the exchange row is R's column 0, as qpb_gi.hip)
-static_assert(NL * RS <= SLOT, "the H transpose is staged over the whole slot");
-// 12 one-wave workgroups per CU need <= 12,800 B of LDS each (qpb_gi.hip,
-// tools/probe/occupancy_probe.hip); the round-4 slot (424 doubles = 13,568 B)
-// ran 11
-static_assert(4 * SLOT * 8 <= kWaveLdsMax, "12 waves per CU by LDS");
+using namespace row16;
 
 // N16: n == 16 (coalesced H loads through an LDS transpose); otherwise the
 // rows are padded with the identity and the padded variables get no bounds
@@ -53,13 +41,9 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
-  // rows past the end of the batch replay its last QP and store nothing (as
-  // in qpb_gi.hip: every lane stays live for the cross-row readlanes)
-  const long long graw = (long long)blockIdx.x * QPB + slot;
-  const bool live = graw < batch;
-  const long long g = live ? graw : batch - 1;
+  const auto [live, g] = ragged_qp(blockIdx.x, slot, batch);
   if constexpr (N16) n = NL;
-  double *base = lds + (((slot & 1) << 1) | (slot >> 1)) * SLOT;  // slots 0, 2, 1, 3 (bank spread)
+  double *base = slot_base(lds, slot);
   double *Lp = base + OFF_L;
   double *R = base + OFF_R;
   double *xch = R;  // the exchange row in R's column 0 (never read by the back substitution)
@@ -93,10 +77,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
     wave_lds_sync();
   } else {
 #pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const double h = Hq[lc * n + (j < n ? j : n - 1)];
-      Lr[j] = (l < n && j < n) ? h : (l == j ? 1.0 : 0.0);
-    }
+    for (int j = 0; j < NL; ++j) Lr[j] = h_padded(Hq, l, lc, n, j);
   }
 #pragma unroll
   for (int j = 0; j < NL; ++j) E[j] = l == j ? 1.0 : 0.0;
@@ -134,13 +115,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
     ey = __builtin_fma(E[k], fk * ik, ey);
   });
   __builtin_amdgcn_sched_barrier(0);
-  // L -> LDS, packed rows, for the final solves (descending j: a lane's dead
-  // entries past its diagonal land first and are overwritten by their owners)
-  unroll<NL>([&](auto J) {
-    constexpr int j = NL - 1 - J;
-    Lp[lrow(l) + j] = Lr[j];
-    wave_lds_sync();
-  });
+  store_l(Lp, l, Lr);  // for the final solves
   // slacks of the unconstrained minimiser x0 = -L^{-T} y: b + D y per row
   double su = bu + ey, sl = bl - ey;
   // |D[l, q:]|^2, the free part of both of the lane's rows (scale of the
@@ -214,10 +189,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
     if (qmax > 0) {
       const double ninv = -invRd;
       double nacc = (l < q) ? Dpl : 0.0;
-      unroll<NL>([&](auto JJ) {
-        constexpr int j = NL - 1 - JJ;
-        if (j > 0 && j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, R[j * NL + l]);  // column 0: no entry above the diagonal
-      });
+      unroll<NL>([&](auto JJ) { back_subst_step<NL - 1 - JJ>(R, l, qmax, nacc, ninv); });
       rm = nacc * ninv;
     }
     // ---- step lengths: exact ratio minimum, then the lowest position reaching it
@@ -352,9 +324,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
         constexpr int j = JJ;
         if (j + 1 < qmax && j >= k && j < q - 1) {
           const double cj = bc<j>(gc), sj = bc<j>(gs);
-          const double e0 = E[j], e1 = E[j + 1];
-          E[j] = __builtin_fma(cj, e0, sj * e1);
-          E[j + 1] = __builtin_fma(-sj, e0, cj * e1);
+          rotate_pair<j>(E, cj, sj);
         }
       });
       --q;
@@ -369,10 +339,7 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
         });
         fn2 = a0 + a1;
       }
-      wave_lds_sync();
-      const double dg = (l < q) ? R[l * NL + l] : 0.0;
-      wave_lds_sync();
-      if (l < q) R[l * NL + l] = 0.0;
+      const double dg = take_diagonal(R, l, q);
       rdg = dg;
       invRd = (l < q) ? rcp1(dg) : 0.0;
     }
@@ -391,39 +358,14 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   wave_lds_sync();
   const double lu = lamb[l], ll = lamb[l + NL];
   wave_lds_sync();
-  // x = -H^{-1} (f + A^T lam), A^T lam = lam_u - lam_l: L y = g, L^T x = -y,
-  // lane-parallel (finished components captured by same-address LDS stores)
+  // x = -H^{-1} (f + A^T lam), A^T lam = lam_u - lam_l
   const double invd = rcp1(Lp[lrow(l) + l]);
   double Lrow[NL];
 #pragma unroll
   for (int j = 0; j < NL; ++j) Lrow[j] = Lp[lrow(l) + j];
   wave_lds_sync();
-  {
-    double acc = fl + lu - ll;
-    unroll<NL>([&](auto K) {
-      constexpr int kk = K;
-      const double yk = bc<kk>(acc * invd);
-      acc = __builtin_fma(-Lrow[kk], yk, acc);
-      xcap[kk] = yk;
-    });
-  }
-  wave_lds_sync();
-  {
-    double acc = xcap[l];
-    wave_lds_sync();
-    unroll<NL>([&](auto K) {
-      constexpr int kk = NL - 1 - K;
-      const double xk = bc<kk>(acc * invd);
-      acc = __builtin_fma(-Lp[lrow(kk) + l], xk, acc);
-      xcap[kk] = xk;
-    });
-  }
-  wave_lds_sync();
-  const double xl = -xcap[l];
-  {
-    const double bad = row_min((__builtin_fabs(xl) < kInf) ? 0.0 : -1.0);
-    if (status == QPB_OK && bad < 0.0) status = QPB_NUMERICAL;
-  }
+  const double xl = solve_x(fl + lu - ll, invd, Lrow, Lp, l, xcap);
+  status = x_status(status, xl);
   if (live && var) {
     xg[g * n + l] = xl;
     lamg[g * 2 * n + l] = lu;

@@ -460,9 +460,9 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
     const long long g = flags[1];
     if (g >= batch) break;
     const double *Hq = Hg + g * (long long)n * n;
-    // BOX: A is implicit and Ag holds lb (n per QP, maybe NULL), so no A row exists to point at; Aq aliases
-    // Hq only to stay a valid pointer and is never read there (its one read is in the !BOX branch of the setup)
-    const double *Aq = BOX ? Hq : Ag + g * (long long)m * n;
+    // BOX: A is implicit and Ag holds lb (n per QP, maybe NULL), so no A row exists to point at: Aq is null
+    // there, and its one read is in the !BOX branch of the setup
+    const double *Aq = BOX ? nullptr : Ag + g * (long long)m * n;
 
     // ------------------------------------------------------------ setup
     clk.tick(10);

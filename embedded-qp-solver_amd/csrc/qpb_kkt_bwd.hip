@@ -27,7 +27,8 @@
 // lam_i dx^T term of dl/dA_i.  The forward solve never produces such a mask.
 //
 // n <= 16, m <= 32 (kkt_bwd_dense_kernel): gi_dense's mapping, one QP per
-// 16-lane DPP row, four per wavefront.  Lane l holds row l of H -> L and rows
+// 16-lane DPP row, four per wavefront, in the LDS slot and with the shared
+// steps of qpb_row16.h.  Lane l holds row l of H -> L and rows
 // l, l + 16 of A -> D from the forward's right-looking sweep, which also
 // carries u.  The orthogonalisation keeps every vector DISTRIBUTED (lane j
 // holds component j): lane j keeps component j of every q_s in 16 statically
@@ -35,29 +36,21 @@
 // LDS, q_s . v is a row_sum per s and v -= sum_s c_s q_s is in-lane.  Two
 // passes per row (classical Gram-Schmidt, repeated) give MGS-grade
 // orthogonality with no dependence between the 16 products of a pass.  R's
-// column t goes to LDS as in gi_dense (column-major, zero diagonal, 1 / R_tt
-// in lane t), so both triangular solves are its lane-parallel DPP-fused back
-// substitution.
-#include "qpb_common.h"
+// column t goes to LDS in the slot's layout (column-major, zero diagonal,
+// 1 / R_tt in lane t), so both triangular solves are the lane-parallel
+// DPP-fused back substitution (row16::back_subst_step).
 #include "qpb_launch.h"  // with qpb.h
+#include "qpb_row16.h"
 
 namespace qpb {
 namespace bwd {
+using namespace row16;
 
-constexpr int NL = 16;  // lanes per QP
-constexpr int QPB = 4;  // QPs per wavefront
-constexpr int RS = 18;  // row stride of the staged 16 x 16 input blocks (conflict-free b128 rows)
-constexpr int L_SIZE = lrow(NL);  // 136
-// per QP: L packed (136) | R column-major 16 x 16 with zero diagonal (the
-// exchange row is its column 0, which the back substitution never reads).
-// After the solves the L part holds the vectors of the outer products.
-constexpr int OFF_L = 0;
-constexpr int OFF_R = L_SIZE;
-constexpr int SLOT = OFF_R + NL * NL + 2;  // 394 doubles, gi_dense's slot
+// The QP's slot is qpb_row16.h's: L packed | R column-major with zero diagonal
+// (the exchange row is its column 0).  After the solves the L part holds the
+// vectors of the outer products.
 constexpr int OFF_X = 0, OFF_DX = 16, OFF_DL = 32, OFF_LM = 64;  // x, dx | dlam, masked lam (32 each)
-static_assert(NL * RS <= SLOT, "the input blocks are staged over the whole slot");
 static_assert(OFF_LM + 32 <= L_SIZE, "the output vectors fit the dead L");
-static_assert(QPB * SLOT * 8 <= kWaveLdsMax, "12 waves per CU by LDS");
 
 // p + q rounded once each and added: the value is symmetric under swapping the
 // two products, so gH == gH^T bit for bit (a contracted fma(a, b, c d) is not)
@@ -80,13 +73,9 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
-  // rows past the end of the batch replay its last QP and store nothing (as
-  // in qpb_gi.hip: every lane stays live for the cross-row readlanes)
-  const long long graw = (long long)blockIdx.x * QPB + slot;
-  const bool live = graw < batch;
-  const long long g = live ? graw : batch - 1;
+  const long long g = ragged_qp(blockIdx.x, slot, batch).g;
   if constexpr (N16) n = NL;
-  double *base = lds + (((slot & 1) << 1) | (slot >> 1)) * SLOT;  // slots 0, 2, 1, 3 (bank spread)
+  double *base = slot_base(lds, slot);
   double *Lp = base + OFF_L;
   double *R = base + OFF_R;
   double *xch = R;
@@ -137,10 +126,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     wave_lds_sync();
   } else {
 #pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const double h = Hq[lc * n + (j < n ? j : n - 1)];
-      Lr[j] = (l < n && j < n) ? h : (l == j ? 1.0 : 0.0);
-    }
+    for (int j = 0; j < NL; ++j) Lr[j] = h_padded(Hq, l, lc, n, j);
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
       const int row = l + NL * r;
@@ -196,13 +182,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     pin(Lr[k]);
   });
   __builtin_amdgcn_sched_barrier(0);
-  // L -> LDS, packed rows, for the last solve (descending j: a lane's dead
-  // entries past its diagonal land first and are overwritten by their owners)
-  unroll<NL>([&](auto J) {
-    constexpr int j = NL - 1 - J;
-    Lp[lrow(l) + j] = Lr[j];
-    wave_lds_sync();
-  });
+  store_l(Lp, l, Lr);  // for the last solve
   // R zeroed in pairs at lane-rotated positions (qpb_gi_box.hip)
 #pragma unroll
   for (int j = 0; j < NL; j += 2)
@@ -289,10 +269,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   {
     const double ninv = -invRd;
     double nacc = -cu;
-    unroll<NL>([&](auto JJ) {
-      constexpr int j = NL - 1 - JJ;
-      if (j > 0 && j < qmax) fmac_bc_nop<j>(nacc, nacc * ninv, R[j * NL + l]);
-    });
+    unroll<NL>([&](auto JJ) { back_subst_step<NL - 1 - JJ>(R, l, qmax, nacc, ninv); });
     y = nacc * invRd;
   }
   // ---- L^T dx = z, the same back substitution on L's rows
@@ -326,9 +303,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   unsigned tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int ls = tid & (NL - 1);
-  const long long gs_raw = (long long)blockIdx.x * QPB + (tid >> 4);
-  const bool lives = gs_raw < batch;
-  const long long gs = lives ? gs_raw : batch - 1;
+  const auto [lives, gs] = ragged_qp(blockIdx.x, tid >> 4, batch);
   const bool vars = N16 || ls < n;
   const double xv = xg[gs * n + (vars ? ls : n - 1)];
   double lmv[MR];  // lam of the lane's rows, 0 outside W
@@ -634,17 +609,9 @@ extern "C" hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, con
     return hipGetLastError();
   }
   const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
-#define QPB_BWD_LAUNCH(MR, N16)                                                                                 \
-  hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR, N16>), dim3((unsigned)blocks), dim3(64), 0, stream, H, A, x, \
-                     lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch)
-  const bool n16 = d->n == 16;
-  if (d->m <= 16) {
-    if (n16) QPB_BWD_LAUNCH(1, true);
-    else QPB_BWD_LAUNCH(1, false);
-  } else {
-    if (n16) QPB_BWD_LAUNCH(2, true);
-    else QPB_BWD_LAUNCH(2, false);
-  }
-#undef QPB_BWD_LAUNCH
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {  // (no FULL form)
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16()>), dim3((unsigned)blocks), dim3(64), 0, stream, H,
+                       A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch);
+  });
   return hipGetLastError();
 }
