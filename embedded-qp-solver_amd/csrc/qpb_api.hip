@@ -226,6 +226,53 @@ extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f
                       "qpb_solve_box launch");
 }
 
+// qpb_solve_box_backward's argument rules after check_desc, up to the pointers
+static int check_bwd_box(const qpb_desc *d) {
+  if (d->m != 2 * d->n)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_backward: m must be 2n (got n=%d m=%d)", d->n, d->m);
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_backward: flags must be 0 (got %d)", d->flags);
+  if (qpb::route_bwd_box(d->n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_solve_box_backward: n=%d outside the backward box kernels (n<=%d)", d->n,
+                qpb::kBwdBoxMaxN);
+  return 0;
+}
+static int check_bwd_box_arrays(const double *H, const double *x, const uint32_t *active, const double *gx,
+                                const double *gH, const double *gf, const double *glb, const double *gub) {
+  if (!H || !x || !active || !gx)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_backward: H, x, active and gx are required");
+  if (!gH && !gf && !glb && !gub)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_backward: at least one of gH, gf, glb and gub is required");
+  return 0;
+}
+
+extern "C" int qpb_solve_box_backward(const qpb_desc *d, const double *H, const double *x, const uint32_t *active,
+                                      const int32_t *status, const double *gx, double *gH, double *gf, double *glb,
+                                      double *gub, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box(d);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_arrays(H, x, active, gx, gH, gf, glb, gub);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_bwd_box(d->n);
+  const long long n = d->n, m = d->m;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const double *xc, const uint32_t *ac, const int32_t *sc,
+          const double *gxc, double *gHc, double *gfc, double *glc, double *guc) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e = qpb_launch_kkt_bwd_box(&c, Hc, xc, ac, sc, gxc, gHc, gfc, glc, guc, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_box_backward launch");
+      },
+      qpb::required(H, n * n), qpb::required(x, n), qpb::required(active, (m + 31) / 32), qpb::optional(status, 1),
+      qpb::required(gx, n), qpb::optional(gH, n * n), qpb::optional(gf, n), qpb::optional(glb, n),
+      qpb::optional(gub, n));
+}
+
 extern "C" int qpb_solve_sections(const qpb_desc *d, const double *H, const double *f, const double *A,
                                   const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
                                   int32_t *iters, unsigned long long *sections, int64_t sections_len,
@@ -373,6 +420,40 @@ extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const
   return 0;
 }
 
+extern "C" int qpb_solve_box_backward_host(const qpb_desc *d, const double *H, const double *x,
+                                           const uint32_t *active, const int32_t *status, const double *gx, double *gH,
+                                           double *gf, double *glb, double *gub) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box(d);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_arrays(H, x, active, gx, gH, gf, glb, gub);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, w = (2 * n + 31) / 32;
+  DevBuf dH, dx, da, ds, dg, oH, of, ol, ou;
+  HIPCHK(up(dH, H, B * n * n * 8), "H");
+  HIPCHK(up(dx, x, B * n * 8), "x");
+  HIPCHK(up(da, active, B * w * 4), "active");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(alloc(oH, gH, B * n * n * 8), "gH");
+  HIPCHK(alloc(of, gf, B * n * 8), "gf");
+  HIPCHK(alloc(ol, glb, B * n * 8), "glb");
+  HIPCHK(alloc(ou, gub, B * n * 8), "gub");
+  rc = qpb_solve_box_backward(d, (double *)dH.p, (double *)dx.p, (uint32_t *)da.p, (int32_t *)ds.p, (double *)dg.p,
+                              (double *)oH.p, (double *)of.p, (double *)ol.p, (double *)ou.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_box_backward_host kernel");
+  HIPCHK(down(gH, oH, B * n * n * 8), "gH D2H");
+  HIPCHK(down(gf, of, B * n * 8), "gf D2H");
+  HIPCHK(down(glb, ol, B * n * 8), "glb D2H");
+  HIPCHK(down(gub, ou, B * n * 8), "gub D2H");
+  return 0;
+}
+
 static int check_ref(const qpb_ref_desc *d) {
   if (!d) return fail(QPB_ERR_INVALID_ARG, "desc is NULL");
   if (d->batch < 0 || d->n < 1 || d->iterations < 0) return fail(QPB_ERR_INVALID_ARG, "bad n/batch/iterations");
@@ -513,4 +594,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above)"; }

@@ -1,0 +1,324 @@
+// qpb_kkt_bwd_box.hip -- the backward pass of a box solve (qpb_solve_box_backward)
+// for gfx950.
+//
+// For lb <= x <= ub the active rows are unit vectors, and the KKT system at a
+// fixed active set collapses.  Variable j is FIXED when its upper-bound bit
+// (j) or its lower-bound bit (n + j) is set in the active mask W; F are the
+// free variables.  With the cotangent g = dl/dx,
+//
+//     dx_fixed = 0                 H_FF dx_F = -g_F
+//     r = g + H dx                 (zero on F by construction)
+//     dl/df = dx                   dl/dH = 1/2 (dx x^T + x dx^T)
+//     dl/dub_j = r_j  if the upper bound of j is active, else 0
+//     dl/dlb_j = r_j  if the lower bound of j is active and the upper is not, else 0
+//
+// One Cholesky of a principal submatrix of H, two triangular solves and one
+// matrix-vector product: no A, no lam, no orthogonalisation, no R.
+//
+// The free block is factored WITHOUT a gather: a fixed (or padded) variable's
+// row of H is replaced by the unit row e_j, its column is zeroed in every
+// other row, and its cotangent becomes 0.  The Cholesky factor of that matrix
+// is the factor of H_FF with identity rows and columns threaded through it,
+// and the two solves leave exact zeros on the fixed variables.  This is the
+// identity padding of n < 16 (row16::h_padded), driven by the mask.
+//
+// n <= 16 (kkt_bwd_box_dense_kernel): kkt_bwd_dense_kernel's mapping, one QP
+// per 16-lane DPP row, four per wavefront, in the LDS slot and with the
+// shared steps of qpb_row16.h.  Lane l holds row l of H twice: untouched (for
+// r) and masked (it becomes row l of L in the right-looking DPP sweep).
+// Every loop bound is a compile-time constant.
+// 16 < n <= 32 (kkt_bwd_box_wave_kernel): one QP per wavefront, L in a 32 x 33
+// LDS block in kkt_bwd_wave_kernel's manner, the untouched H in a second one.
+#include "qpb_launch.h"  // with qpb.h
+#include "qpb_row16.h"
+
+namespace qpb {
+namespace bwdbox {
+using namespace row16;
+
+// the vectors of the outer product, over the dead L
+constexpr int OFF_X = 0, OFF_DX = 16;
+static_assert(OFF_DX + 16 <= L_SIZE, "the output vectors fit the dead L");
+
+// p + q rounded once each and added: the value is symmetric under swapping the
+// two products, so gH == gH^T bit for bit (a contracted fma(a, b, c d) is not)
+__device__ __forceinline__ double sym2(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double p = a * b;
+  const double q = c * d;
+  return p + q;
+}
+
+// N16: n == 16 (coalesced loads and stores through this QP's LDS slot);
+// otherwise the rows are padded with the identity.
+template <bool N16>
+__global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
+    const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
+    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch) {
+  __shared__ double lds[QPB * SLOT];
+  const int l = threadIdx.x & (NL - 1);
+  const int slot = threadIdx.x >> 4;
+  const auto [live, g] = ragged_qp(blockIdx.x, slot, batch);
+  if constexpr (N16) n = NL;
+  double *base = slot_base(lds, slot);
+  double *Lp = base + OFF_L;
+  double *xcap = base + OFF_R;  // the solves' captured components (16)
+
+  // ------------------------------------------------------------------ load
+  const bool var = N16 || l < n;
+  const int lc = var ? l : n - 1;
+  const double *Hq = Hg + g * (long long)n * n;
+  const bool ok = statg ? statg[g] == QPB_OK : true;
+  // a QP that is not QPB_OK has no fixed variable and stores zeros
+  const uint32_t W = ok ? actg[g] : 0u;
+  const uint32_t nmask = (1u << n) - 1u;  // n <= 16
+  const uint32_t fixed = (W | (W >> n)) & nmask;
+  const double gv = gxg[g * n + lc];
+  const double xv = xg[g * n + lc];
+  double Hr[NL];  // row l of H, untouched
+  if constexpr (N16) {
+    // coalesced 16-byte loads, two whole rows of each of the wave's 4 QPs per
+    // instruction; the rows reach their owner lanes through a transpose in
+    // this QP's LDS slot (qpb_kkt_bwd.hip)
+    const int hr = l >> 3, hc = 2 * (l & 7);
+    double2 hv[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) hv[t] = *reinterpret_cast<const double2 *>(&Hq[(2 * t + hr) * NL + hc]);
+    wave_lds_sync();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) *reinterpret_cast<double2 *>(&base[(2 * t + hr) * RS + hc]) = hv[t];
+    wave_lds_sync();
+    lds_row16(&base[l * RS], Hr);
+    wave_lds_sync();
+  } else {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) Hr[j] = h_padded(Hq, l, lc, n, j);
+  }
+  // the masked matrix: e_l on a fixed or padded lane, zero in fixed columns
+  // (the padded columns are zero already)
+  const bool fix = !var || ((fixed >> l) & 1u);
+  double Lr[NL];  // becomes row l of L
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    const double unit = l == j ? 1.0 : 0.0;
+    Lr[j] = fix ? unit : (((fixed >> j) & 1u) ? 0.0 : Hr[j]);
+  }
+
+  // ---- H~ = L L^T: kkt_bwd_dense_kernel's right-looking sweep without its E
+  // rows.  Step k: the pivot row is read straight from lane k by the DPP-fused
+  // FMAs; the sched_barrier and the rsq chain keep every write of Lr[j]
+  // (previous step) well over two instructions before these reads.
+  double invLd = 0.0;
+  unroll<NL>([&](auto K) {
+    constexpr int k = K;
+    __builtin_amdgcn_sched_barrier(0);
+    const double akk = bc<k>(Lr[k]);
+    const double ik = rsq1(akk);
+    const double ik2 = ik * ik;
+    const double nc = -(Lr[k] * ik2);
+    invLd = l == k ? ik : invLd;
+    pin(invLd);
+    unroll<NL - 1 - k>([&](auto J) {
+      constexpr int j = k + 1 + J;
+      fmac_bc<k>(Lr[j], Lr[j], nc);
+    });
+    Lr[k] *= ik;
+    pin(Lr[k]);
+  });
+  __builtin_amdgcn_sched_barrier(0);
+  store_l(Lp, l, Lr);  // for the second solve
+
+  // ---- dx = -H~^{-1} g~: exact zeros on the fixed lanes
+  double dx = solve_x(fix ? 0.0 : gv, invLd, Lr, Lp, l, xcap);
+  if (fix || !ok) dx = 0.0;
+  // ---- r = g + H dx from the untouched row, dx_k read from lane k by the FMA
+  double r = gv;
+  pin(dx);
+  dpp_ready(dx);
+  unroll<NL>([&](auto K) { fmac_bc<K>(r, dx, Hr[K]); });
+
+  // ------------------------------------------------------------------ store
+  const bool up = (W >> l) & 1u, lo = (W >> (l + n)) & 1u;
+  if (live && var) {
+    if (gfg) gfg[g * n + l] = dx;
+    if (gubg) gubg[g * n + l] = up ? r : 0.0;
+    if (glbg) glbg[g * n + l] = (lo && !up) ? r : 0.0;
+  }
+  if (!gHg) return;  // wave-uniform
+  // the vectors of the outer product, over the dead L
+  wave_lds_sync();
+  base[OFF_X + l] = (ok && var) ? xv : 0.0;
+  base[OFF_DX + l] = dx;
+  wave_lds_sync();
+  const double *X = base + OFF_X, *DX = base + OFF_DX;
+  if constexpr (N16) {
+    // lane l writes columns 2 (l & 7), +1 of rows 2 t + (l >> 3): 256 contiguous bytes per QP and store
+    const int hr = l >> 3, hc = 2 * (l & 7);
+    const double x0 = X[hc], x1 = X[hc + 1], d0 = DX[hc], d1 = DX[hc + 1];
+    if (live) {
+      double *o = gHg + g * (long long)(NL * NL);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int row = 2 * t + hr;
+        const double dr = DX[row], xr = X[row];
+        *reinterpret_cast<double2 *>(&o[row * NL + hc]) =
+            make_double2(0.5 * sym2(dr, x0, xr, d0), 0.5 * sym2(dr, x1, xr, d1));
+      }
+    }
+  } else {
+    // element e of the row-major output at lane e mod 16
+    if (live) {
+      double *o = gHg + g * (long long)n * n;
+      for (int e = l; e < n * n; e += NL) {
+        const int row = e / n, col = e - row * n;
+        o[e] = 0.5 * sym2(DX[row], X[col], X[row], DX[col]);
+      }
+    }
+  }
+}
+
+// ---- 16 < n <= 32: one QP per wavefront ---------------------------------------
+// kkt_bwd_wave_kernel's layout: L in the lower triangle of a 32 x 33 block (odd
+// stride: rows and columns are both conflict-free), the untouched H in a
+// second block for r.  H is padded to 32 x 32 with the identity, and the fixed
+// variables are padding inside it: the same loops with the same constant
+// bounds.  Lane j < 32 holds component j of the running vectors.
+constexpr int WN = 32;      // variables (lanes that carry a component)
+constexpr int WS = WN + 1;  // row stride
+constexpr int W_L = 0, W_H = WN * WS, W_X = 2 * WN * WS, W_DX = W_X + 32, W_SIZE = W_DX + 32;
+constexpr int W_COL = WN + 2;  // the pivot column of a factorisation step, zero past the matrix
+static_assert((W_SIZE + W_COL) * 8 <= 20480, "8 waves per CU by LDS");
+
+__global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
+    const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
+    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch) {
+  __shared__ double lds[W_SIZE];
+  // an object of its own: the factorisation's trailing update reads it while
+  // it writes L, and the compiler can then batch the reads of an unrolled trip
+  __shared__ double colk[W_COL];
+  const int lane = threadIdx.x;
+  const int i = lane & (WN - 1), half = lane >> 5;
+  const bool low = lane < WN;      // the lanes that carry a component
+  const long long g = blockIdx.x;  // one workgroup of one wave per QP: always < batch
+  double *Lm = lds + W_L, *Hm = lds + W_H, *X = lds + W_X, *DX = lds + W_DX;
+  const double *Hq = Hg + g * (long long)n * n;
+  const bool ok = statg ? statg[g] == QPB_OK : true;
+  // The active mask as one 64-bit word (wave-uniform): 16 < n, so 2n bits
+  // take two words, and bit n + j of a lower bound crosses from word 0 into
+  // word 1 at j = 32 - n.  A QP that is not QPB_OK has no fixed variable.
+  unsigned long long W = 0;
+  if (ok) {
+    W = actg[g * 2] | ((unsigned long long)actg[g * 2 + 1] << 32);
+    if (n < 32) W &= (1ull << (2 * n)) - 1ull;
+  }
+  const uint32_t nmask = (uint32_t)((1ull << n) - 1ull);
+  const uint32_t upw = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)W & nmask));
+  const uint32_t low_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(W >> n) & nmask));
+  const uint32_t fixed = upw | low_w;
+  // H untouched (zero padding) and masked: e_j on a fixed or padded variable, zero in its column
+  for (int e = lane; e < WN * WN; e += 64) {
+    const int row = e >> 5, col = e & (WN - 1);
+    const bool in = row < n && col < n;
+    const double h = Hq[in ? row * n + col : 0];
+    const bool fx = !in || ((fixed >> row) & 1u) || ((fixed >> col) & 1u);
+    Hm[row * WS + col] = in ? h : 0.0;
+    Lm[row * WS + col] = fx ? (row == col ? 1.0 : 0.0) : h;
+  }
+  if (lane < W_COL) colk[lane] = 0.0;
+  const bool var = lane < n;
+  const bool fix = !var || ((fixed >> i) & 1u);  // (lane < n <= 32: i == lane)
+  const double gv = var ? gxg[g * n + lane] : 0.0;
+  double ui = fix ? 0.0 : gv;       // the running g~, u_k = (L^{-1} g~)_k from step k on
+  double invLd = var ? 0.0 : 1.0;   // 1 / L[lane][lane] (1 on the padding)
+  wave_lds_sync();
+
+  // ---- H~ = L L^T (right-looking, in place) and u = L^{-1} g~: kkt_bwd_wave_kernel's
+  // loop.  Step k updates the whole rows k+1.. of the symmetric trailing
+  // block, the two halves of the wave on alternate columns (the last trip of
+  // the upper half may touch the row's padding word, colk is zero there)
+  for (int k = 0; k < n; ++k) {
+    const double ik = rsq(Lm[k * WS + k]);
+    const double uk = readlane_d(ui, k) * ik;
+    const double lik = i >= k ? Lm[i * WS + k] * ik : 0.0;
+    wave_lds_sync();
+    if (half == 0) {
+      colk[i] = i > k ? lik : 0.0;
+      if (i >= k) Lm[i * WS + k] = lik;
+    }
+    if (lane == k) {
+      ui = uk;
+      invLd = ik;
+    } else if (low && lane > k) {
+      ui = __builtin_fma(-lik, uk, ui);
+    }
+    wave_lds_sync();
+    const double nl = i > k ? -lik : 0.0;
+    double *row = Lm + i * WS + k + 1 + half;
+    const double *col = colk + k + 1 + half;
+    const int trips = (WN - k) / 2;
+#pragma unroll 4
+    for (int jj = 0; jj < trips; ++jj) row[2 * jj] = __builtin_fma(nl, col[2 * jj], row[2 * jj]);
+    wave_lds_sync();
+  }
+
+  // ---- L^T dx = -u
+  double dx = low ? -ui : 0.0;
+#pragma unroll
+  for (int j = WN - 1; j >= 0; --j) {
+    const double dj = readlane_d(dx * invLd, j);
+    const double lj = lane < j ? Lm[j * WS + i] : 0.0;
+    dx = lane == j ? dj : __builtin_fma(-lj, dj, dx);
+  }
+  if (!ok || fix) dx = 0.0;
+  if (low) {
+    X[lane] = (ok && var) ? xg[g * n + lane] : 0.0;
+    DX[lane] = dx;
+  }
+  wave_lds_sync();
+
+  // ---- r = g + H dx from the untouched rows (zero past n)
+  if (var) {
+    double r0 = gv, r1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < WN; j += 2) {
+      r0 = __builtin_fma(Hm[lane * WS + j], DX[j], r0);
+      r1 = __builtin_fma(Hm[lane * WS + j + 1], DX[j + 1], r1);
+    }
+    const double r = r0 + r1;
+    const bool up = (upw >> lane) & 1u, lo = (low_w >> lane) & 1u;
+    if (gfg) gfg[g * n + lane] = dx;
+    if (gubg) gubg[g * n + lane] = up ? r : 0.0;
+    if (glbg) glbg[g * n + lane] = (lo && !up) ? r : 0.0;
+  }
+  if (gHg) {
+    double *o = gHg + g * (long long)n * n;
+    for (int e = lane; e < n * n; e += 64) {
+      const int row = e / n, col = e - row * n;
+      o[e] = 0.5 * sym2(DX[row], X[col], X[row], DX[col]);
+    }
+  }
+}
+
+}  // namespace bwdbox
+}  // namespace qpb
+
+extern "C" hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H, const double *x,
+                                             const uint32_t *active, const int32_t *status, const double *gx,
+                                             double *gH, double *gf, double *glb, double *gub, hipStream_t stream) {
+  using namespace qpb::bwdbox;
+  if (d->n > 16) {  // one workgroup of one wave per QP
+    hipLaunchKernelGGL(kkt_bwd_box_wave_kernel, dim3((unsigned)d->batch), dim3(64), 0, stream, H, x, active, status, gx,
+                       gH, gf, glb, gub, d->n, (long long)d->batch);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + QPB - 1) / QPB;
+  if (d->n == 16)
+    hipLaunchKernelGGL(kkt_bwd_box_dense_kernel<true>, dim3((unsigned)blocks), dim3(64), 0, stream, H, x, active,
+                       status, gx, gH, gf, glb, gub, d->n, (long long)d->batch);
+  else
+    hipLaunchKernelGGL(kkt_bwd_box_dense_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, stream, H, x, active,
+                       status, gx, gH, gf, glb, gub, d->n, (long long)d->batch);
+  return hipGetLastError();
+}

@@ -37,6 +37,10 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, c
                                            const double *lam, const uint32_t *active, const int32_t *status,
                                            const double *gx, double *gH, double *gf, double *gA, double *gb,
                                            hipStream_t stream);
+// qpb_solve_box_backward: d->m == 2 d->n, n <= 32 (qpb_kkt_bwd_box.hip); any of gH, gf, glb, gub may be NULL
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H, const double *x,
+                                               const uint32_t *active, const int32_t *status, const double *gx,
+                                               double *gH, double *gf, double *glb, double *gub, hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

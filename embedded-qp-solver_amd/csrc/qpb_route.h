@@ -106,6 +106,26 @@ static_assert(route_bwd(33, 0).step == 0 && route_bwd(32, 65).step == 0 && route
 static_assert(route_bwd(kBwdMaxN, kBwdMaxM).step > 0 && route_bwd(kBwdMaxN + 1, 1).step == 0 &&
               route_bwd(1, kBwdMaxM + 1).step == 0);
 
+// qpb_solve_box_backward: the two wavefront-level classes of qpb_kkt_bwd_box.hip,
+// named by the forward box kernel whose lane mapping they share (m = 2n
+// implicit); above them there is no backward kernel yet: step 0, and the call
+// is unsupported.
+constexpr Route route_bwd_box(int n) {
+  if (n <= 16) return {Kernel::gi_box, step_of(Kernel::gi_box)};
+  if (n <= 32) return {Kernel::gi_wave_box, step_of(Kernel::gi_wave_box)};
+  return {Kernel::gi_gram_box, 0};
+}
+constexpr int kBwdBoxMaxN = 32;  // the limit route_bwd_box's step 0 stands for
+
+static_assert(route_bwd_box(1).kernel == Kernel::gi_box && route_bwd_box(16).kernel == Kernel::gi_box);
+static_assert(route_bwd_box(17).kernel == Kernel::gi_wave_box && route_bwd_box(32).kernel == Kernel::gi_wave_box);
+static_assert(route_bwd_box(16).step == 1LL << 27 && route_bwd_box(32).step == 1LL << 25);
+static_assert(route_bwd_box(33).step == 0 && route_bwd_box(128).step == 0);
+static_assert(route_bwd_box(kBwdBoxMaxN).step > 0 && route_bwd_box(kBwdBoxMaxN + 1).step == 0);
+// the backward of a box solve runs wherever the forward's own class does, up to the limit
+static_assert(route_bwd_box(16).kernel == route(16, 32, 0, true).kernel &&
+              route_bwd_box(17).kernel == route(17, 34, 0, true).kernel);
+
 // One array of a batched call: per_qp elements per QP from base.  Only an
 // optional array may be NULL, and then it is NULL in every chunk.
 template <class T>

@@ -13,6 +13,7 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve(H, f)                -> qpb_solve, m=0  (test/qp_ref.py:35 semantics)
     solve_eq(H, f, A, b, meq)  -> qpb_solve_eq    (rows 0 .. meq-1 of A are equalities)
     solve_backward(H, A, sol, gx) -> qpb_solve_backward (gradients of a solve; autograd: qpb.diff)
+    solve_box_backward(H, sol, gx) -> qpb_solve_box_backward (gradients of a box solve, n <= 32)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
     ref_generate(n, B, seed)   -> qpb_ref_generate (the reference generator, bit for bit)
@@ -76,6 +77,10 @@ _lib.qpb_solve_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
 _lib.qpb_solve_backward_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
+_lib.qpb_solve_box_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
+_lib.qpb_solve_box_backward.restype = ctypes.c_int
+_lib.qpb_solve_box_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
+_lib.qpb_solve_box_backward_host.restype = ctypes.c_int
 _lib.qpb_ref_solve.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 6
 _lib.qpb_ref_solve.restype = ctypes.c_int
 _lib.qpb_ref_solve_host.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 5
@@ -344,6 +349,81 @@ def solve_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
                                       p(gA), p(gb))
     _check(rc, "qpb_solve_backward_host")
     return gH, gf, gA, gb
+
+
+BOX_NEED_ALL = ("H", "f", "lb", "ub")
+
+
+def _box_need_set(need) -> set:
+    need = set(need)
+    if not need or not need <= set(BOX_NEED_ALL):
+        raise ValueError(f"need must be a non-empty subset of {BOX_NEED_ALL}")
+    return need
+
+
+def solve_box_backward(H, sol: Solution, gx, *, need=BOX_NEED_ALL, stream=None):
+    """Gradients of a box solve (qpb_solve_box_backward): given ``sol`` from
+    ``solve_box`` on (H, f, lb, ub) and the cotangent ``gx = dl/dx`` (B, n),
+    returns ``(gH, gf, glb, gub)`` = dl/dH (B,n,n), dl/df, dl/dlb, dl/dub (B,n)
+    at fixed active set (qpb.h has the contract).  Only ``sol.x``,
+    ``sol.active`` and ``sol.status`` are read.  Entries left out of ``need``
+    come back as None and are neither computed nor stored.  ``sol.status`` may
+    be None: every QP then counts as OK.  QPs whose status is not OK get zeros.
+    n <= 32; torch CUDA float64 tensors as for ``solve_box``.
+    """
+    import torch
+    if not (H.is_cuda and gx.is_cuda):
+        raise ValueError("qpb.solve_box_backward expects CUDA (HIP) tensors; use solve_box_backward_host for numpy")
+    B, n = gx.shape
+    for t in (H, gx):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+    if H.shape != (B, n, n):
+        raise ValueError("shape mismatch")
+    need = _box_need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if (sol.active is None or not sol.active.is_cuda or not sol.active.is_contiguous()
+            or sol.active.shape != (B, (2 * n + 31) // 32) or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(2n/32)) CUDA tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(B, n, n) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    glb = new(B, n) if "lb" in need else None
+    gub = new(B, n) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_box_backward(ctypes.byref(d), _ptr(H), _ptr(sol.x), _ptr(sol.active), _ptr(sol.status),
+                                     _ptr(gx), _ptr(gH), _ptr(gf), _ptr(glb), _ptr(gub), _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_backward")
+    return gH, gf, glb, gub
+
+
+def solve_box_backward_host(H, sol: Solution, gx, *, need=BOX_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_box_backward_host): ``solve_box_backward`` with host arrays."""
+    import numpy as np
+    need = _box_need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    if H.shape != (B, n, n) or x.shape != (B, n) or act.shape != (B, (2 * n + 31) // 32):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros((B, n, n)) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    glb = np.zeros((B, n)) if "lb" in need else None
+    gub = np.zeros((B, n)) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_backward_host(ctypes.byref(d), p(H), p(x), p(act), p(st), p(gx), p(gH), p(gf), p(glb),
+                                          p(gub))
+    _check(rc, "qpb_solve_box_backward_host")
+    return gH, gf, glb, gub
 
 
 def active_mask_to_bool(active, m: int):

@@ -8,6 +8,9 @@ solution's active set, on the GPU).  This module imports torch at the top;
     x, status = qpb.diff.solve(H, f, A, b, meq=2)   # H, f, A, b may require grad
     loss = (w * x).sum()
     loss.backward()                                 # H.grad, f.grad, A.grad, b.grad
+
+``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
+and ub (``qpb.solve_box_backward``, n <= 32).
 """
 from __future__ import annotations
 
@@ -41,6 +44,45 @@ class QPFunction(torch.autograd.Function):
         # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
         gH, gf, gA, gb = qpb.solve_backward(H, A, sol, gx.contiguous(), need=wanted)
         return gH, gf, gA, gb, None, None, None
+
+
+class BoxQPFunction(torch.autograd.Function):
+    """x*(H, f, lb, ub) of min 1/2 x'Hx + f'x s.t. lb <= x <= ub."""
+
+    @staticmethod
+    def forward(ctx, H, f, lb, ub, max_iter, feas_tol):
+        H, f = H.contiguous(), f.contiguous()
+        lb = None if lb is None else lb.contiguous()
+        ub = None if ub is None else ub.contiguous()
+        sol = qpb.solve_box(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.has = (True, True, lb is not None, ub is not None)
+        ctx.save_for_backward(H, sol.x, sol.active, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        H, x, active, status = ctx.saved_tensors
+        names = ("H", "f", "lb", "ub")
+        wanted = [k for k, w, has in zip(names, ctx.needs_input_grad[:4], ctx.has) if w and has]
+        if not wanted:
+            return (None,) * 6
+        sol = qpb.Solution(x, None, active, status, None)
+        # on torch's current stream; above n = 32 this raises QPBError(ERR_UNSUPPORTED)
+        gH, gf, glb, gub = qpb.solve_box_backward(H, sol, gx.contiguous(), need=wanted)
+        return gH, gf, glb, gub, None, None
+
+
+def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0):
+    """Differentiable batched box solve (``qpb.solve_box`` with gradients):
+    returns ``(x, status)``; ``x`` carries gradients to whichever of H, f, lb
+    and ub require them, ``status`` (int32 per QP) is not differentiable.  A
+    bound passed as None gets no gradient.  QPs whose status is not OK
+    contribute zero gradients.  The gradient is the derivative at fixed active
+    set (qpb.h, qpb_solve_box_backward).  The forward solves every shape
+    ``qpb.solve_box`` does (n <= 128); the backward needs n <= 32 and raises
+    ``QPBError(ERR_UNSUPPORTED)`` above that."""
+    return BoxQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol))
 
 
 def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):

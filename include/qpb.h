@@ -13,6 +13,7 @@
  *   north_star active-set over (H, f, A, b)              qpb_solve(m > 0)
  *   ... with equality rows, solve_qp(P, q, G, h, A, b)    qpb_solve_eq
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
+ *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -278,8 +279,8 @@ int qpb_solve_eq_host(const qpb_desc *desc, int32_t meq, const double *H,
  * QPB_ERR_INVALID_ARG; a missing device last.
  * Limits: n <= 16, m <= 32 runs four QPs per wavefront, the rest of n <= 32,
  * m <= 64 one QP per wavefront (qpb_kkt_bwd.hip).  The n <= 128 class needs a
- * workgroup-level kernel, and the backward of qpb_solve_box (gradients for lb
- * and ub, the active rows as unit vectors) is not there either: follow-ups.
+ * workgroup-level kernel: a follow-up.  The backward of qpb_solve_box is
+ * qpb_solve_box_backward, below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_backward(const qpb_desc *desc, const double *H, const double *A,
 		       const double *x, const double *lam,
@@ -311,6 +312,67 @@ int qpb_solve_backward_host(const qpb_desc *desc, const double *H,
 int qpb_solve_box(const qpb_desc *desc, const double *H, const double *f,
 		  const double *lb, const double *ub, double *x, double *lam,
 		  uint32_t *active, int32_t *status, int32_t *iters, void *stream);
+
+/* The backward pass of qpb_solve_box: the vector-Jacobian product of
+ * x*(H, f, lb, ub).  Given a box solve's x, active and status and the cotangent
+ * gx = dl/dx (n per QP), the KKT system of qpb_solve_backward at FIXED active
+ * set with the rows of A = [I; -I] as unit vectors.  Variable j is fixed when
+ * its upper-bound bit (j) or its lower-bound bit (n + j) is set in `active`,
+ * F are the free variables:
+ *
+ *     dx_fixed = 0,   H_FF dx_F = -gx_F,   r = gx + H dx   (zero on F)
+ *
+ *     gf  = dx                            (n per QP)
+ *     gH  = 1/2 (dx x^T + x dx^T)         (n x n; symmetric bit for bit)
+ *     gub_j = r_j  if the upper bound of j is active, else 0           (n)
+ *     glb_j = r_j  if the lower bound of j is active and the upper
+ *                  is not, else 0                                      (n)
+ *
+ * One Cholesky of H with the fixed variables' rows and columns replaced by
+ * the identity, two triangular solves and one matrix-vector product per QP.
+ * lam, f, lb and ub are not arguments: no output depends on them.  These are
+ * qpb_solve_backward's gradients on the same QP written with A = [I; -I],
+ * b = [ub; -lb]: gub = gb[:n], glb = -gb[n:].  At fixed active set:
+ *   weakly active   a set bit counts as active whatever its multiplier, so
+ *                   the result is one of the two one-sided derivatives.
+ *   both bits set   (a variable pinned by lb = ub, or a caller's own mask)
+ *                   the upper bound counts and the lower bound gets 0:
+ *                   qpb_solve_backward's row-order rule for a dependent row.
+ *   all fixed       gf = 0, gH = 0 and r = gx.
+ *   none fixed      dx = -H^{-1} gx and glb = gub = 0.
+ *   bits >= 2n      bits at positions >= 2n in the last word of `active` are
+ *                   ignored.
+ * desc is the forward qpb_solve_box call's: n, m (which must be 2n) and batch
+ * are used, max_iter and feas_tol are ignored, flags must be 0.  x and active
+ * (ceil(2n/32) words per QP; bits 0..n-1 the upper bounds, n..2n-1 the lower
+ * bounds) in qpb_solve_box's layouts.
+ *   required        H, x, active and gx.
+ *   status          may be NULL: every QP then counts as QPB_OK.
+ *   gH, gf, glb, gub  each may be NULL: that gradient is neither computed nor
+ *                   stored; at least one must be given.
+ * Every element of every non-NULL output of every QP is written, and nothing
+ * else; a QP whose status is not QPB_OK gets zeros in all of them; a QP's
+ * outputs depend on its own inputs only.
+ * Errors, in order: the descriptor as qpb_solve_box (m != 2n
+ * QPB_ERR_INVALID_ARG); flags != 0 QPB_ERR_INVALID_ARG; n > 32
+ * QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are looked
+ * at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits: n <= 16 runs four QPs per wavefront, 16 < n <= 32 one QP per
+ * wavefront (qpb_kkt_bwd_box.hip).  The n in (32, 128] class of qpb_solve_box
+ * needs the workgroup-level kernel that qpb_solve_backward also lacks: a
+ * follow-up.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_box_backward(const qpb_desc *desc, const double *H,
+			   const double *x, const uint32_t *active,
+			   const int32_t *status, const double *gx, double *gH,
+			   double *gf, double *glb, double *gub, void *stream);
+
+/* Same with host pointers, as qpb_solve_host. */
+int qpb_solve_box_backward_host(const qpb_desc *desc, const double *H,
+				const double *x, const uint32_t *active,
+				const int32_t *status, const double *gx,
+				double *gH, double *gf, double *glb,
+				double *gub);
 
 /* Reference-semantics solvers (qp_solvers.c replicas). */
 typedef enum qpb_ref_mode {
