@@ -208,6 +208,132 @@ extern "C" int qpb_solve_backward(const qpb_desc *d, const double *H, const doub
       qpb::optional(gf, n), qpb::optional(gA, m * n), qpb::optional(gb, m));
 }
 
+// ---- one H and / or one A for the whole batch --------------------------------
+// `shared` with the bits that select nothing taken out: QPB_SHARED_A at m == 0
+static int32_t shared_of(const qpb_desc *d, int32_t shared) { return d->m == 0 ? shared & ~QPB_SHARED_A : shared; }
+
+// qpb_solve_shared's argument rules after check_desc: check_eq's, with the
+// shared bits beside the flags and a size limit and message of its own
+static int check_shared(const qpb_desc *d, int32_t meq, int32_t shared) {
+  if (meq < 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared: meq < 0");
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared: flags must be 0 (got %d)", d->flags);
+  if (shared & ~(QPB_SHARED_H | QPB_SHARED_A))
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared: shared must be a combination of QPB_SHARED_H and QPB_SHARED_A (got %d)",
+                shared);
+  if (shared_of(d, shared) != 0 && qpb::route_shared(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_solve_shared: n=%d m=%d outside the kernels with a shared H or A (n<=%d, m<=%d)", d->n, d->m,
+                qpb::kSharedMaxN, qpb::kSharedMaxM);
+  return 0;
+}
+
+extern "C" int qpb_solve_shared(const qpb_desc *d, int32_t meq, int32_t shared, const double *H, const double *f,
+                                const double *A, const double *b, double *x, double *lam, uint32_t *active,
+                                int32_t *status, int32_t *iters, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_shared(d, meq, shared);
+  if (rc) return rc;
+  shared = shared_of(d, shared);
+  // nothing shared: the call is qpb_solve_eq, with its remaining rules
+  if (shared == 0) return qpb_solve_eq(d, meq, H, f, A, b, x, lam, active, status, iters, stream);
+  if (meq > d->m) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared: meq=%d > m=%d", meq, d->m);
+  if (d->batch == 0) return 0;
+  rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_shared(d->n, d->m);
+  qpb_gi_shared_launcher *const fn =
+      r.kernel == qpb::Kernel::gi_dense ? qpb_launch_gi_shared : qpb_launch_gi_wave_shared;
+  const long long n = d->n, m = d->m;
+  // a shared operand's QP stride is 0, in the kernels and in the chunk walk
+  const long long sH = (shared & QPB_SHARED_H) ? 0 : n * n, sA = (shared & QPB_SHARED_A) ? 0 : m * n;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const double *fc, const double *Ac, const double *bc, double *xc,
+          double *lc, uint32_t *ac, int32_t *sc, int32_t *ic) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e = fn(&c, meq, sH, sA, Hc, fc, Ac, bc, xc, lc, ac, sc, ic, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_shared launch");
+      },
+      qpb::required(H, sH), qpb::required(f, n), qpb::optional(A, sA), qpb::optional(b, m), qpb::required(x, n),
+      qpb::optional(lam, m), qpb::optional(active, (m + 31) / 32), qpb::required(status, 1), qpb::optional(iters, 1));
+}
+
+// qpb_solve_shared_backward's argument rules after check_desc, up to the pointers
+static int check_shared_bwd(const qpb_desc *d, int32_t shared) {
+  if (d->flags != 0)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared_backward: flags must be 0 (got %d)", d->flags);
+  if (shared & ~(QPB_SHARED_H | QPB_SHARED_A))
+    return fail(QPB_ERR_INVALID_ARG,
+                "qpb_solve_shared_backward: shared must be a combination of QPB_SHARED_H and QPB_SHARED_A (got %d)",
+                shared);
+  if (shared_of(d, shared) != 0 && qpb::route_shared_bwd(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_solve_shared_backward: n=%d m=%d outside the kernels with a shared H or A (n<=%d, m<=%d)", d->n,
+                d->m, qpb::kSharedMaxN, qpb::kSharedMaxM);
+  return 0;
+}
+
+extern "C" int qpb_solve_shared_backward(const qpb_desc *d, int32_t shared, const double *H, const double *A,
+                                         const double *x, const double *lam, const uint32_t *active,
+                                         const int32_t *status, const double *gx, double *gH, double *gf, double *gA,
+                                         double *gb, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_shared_bwd(d, shared);
+  if (rc) return rc;
+  shared = shared_of(d, shared);
+  // nothing shared: the call is qpb_solve_backward, with its remaining rules
+  if (shared == 0) return qpb_solve_backward(d, H, A, x, lam, active, status, gx, gH, gf, gA, gb, stream);
+  if (d->batch == 0) return 0;
+  rc = check_bwd_arrays(d, H, A, x, lam, active, gx, gH, gf, gA, gb);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_shared_bwd(d->n, d->m);
+  const long long n = d->n, m = d->m, B = d->batch;
+  if (m == 0) gA = gb = nullptr;  // ignored
+  const long long sH = (shared & QPB_SHARED_H) ? 0 : n * n, sA = (shared & QPB_SHARED_A) ? 0 : m * n;
+  // the gradients pass 2 sums; pass 1 is launched without them
+  double *const sumH = (shared & QPB_SHARED_H) ? gH : nullptr, *const sumA = (shared & QPB_SHARED_A) ? gA : nullptr;
+  double *const gH1 = (shared & QPB_SHARED_H) ? nullptr : gH, *const gA1 = (shared & QPB_SHARED_A) ? nullptr : gA;
+  const hipStream_t st = (hipStream_t)stream;
+  // pass 1 over the batch in chunks; gf1 and gb1 are the caller's, or the workspace's where pass 2 needs them
+  auto pass1 = [&](double *gf1, double *gb1) {
+    return qpb::for_each_chunk(
+        B, r.step,
+        [&](long long count, const double *Hc, const double *Ac, const double *xc, const double *lc,
+            const uint32_t *ac, const int32_t *sc, const double *gxc, double *gHc, double *gfc, double *gAc,
+            double *gbc) {
+          qpb_desc c = *d;
+          c.batch = count;
+          const hipError_t e = qpb_launch_kkt_bwd_shared(&c, sH, sA, Hc, Ac, xc, lc, ac, sc, gxc, gHc, gfc, gAc, gbc, st);
+          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_shared_backward launch");
+        },
+        qpb::required(H, sH), qpb::optional(A, sA), qpb::required(x, n), qpb::optional(lam, m),
+        qpb::optional(active, (m + 31) / 32), qpb::optional(status, 1), qpb::required(gx, n),
+        qpb::optional(gH1, n * n), qpb::optional(gf1, n), qpb::optional(gA1, m * n), qpb::optional(gb1, m));
+  };
+  if (!sumH && !sumA) return pass1(gf, gb);  // the summed gradients are not wanted: pass 1 alone
+  // workspace: the slots, then dx (B n) where gf is not given, then gb (B m)
+  // where gA is summed and gb is not given
+  const long long slot_doubles = qpb::sum_plan(B).slots * qpb::sum_slot_doubles(d->n, d->m);
+  const long long ws_dx = gf ? 0 : B * n, ws_gb = (sumA && !gb) ? B * m : 0;
+  const hipError_t e = qpb_with_workspace(st, (size_t)(slot_doubles + ws_dx + ws_gb) * 8, [&](void *ws) {
+    double *const slots = (double *)ws;
+    double *const dx = gf ? gf : slots + slot_doubles;
+    double *const gbs = gb ? gb : sumA ? slots + slot_doubles + ws_dx : nullptr;
+    rc = pass1(dx, gbs);
+    if (rc) return hipSuccess;  // reported through rc
+    return qpb_launch_kkt_bwd_sum(d, x, dx, gbs, lam, active, status, slots, sumH, sumA, st);
+  });
+  if (rc) return rc;
+  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_shared_backward sum launch");
+}
+
 extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
                              const double *ub, double *x, double *lam, uint32_t *active, int32_t *status,
                              int32_t *iters, void *stream) {
@@ -330,17 +456,20 @@ static hipError_t down(void *dst, const DevBuf &b, size_t bytes) {
     if (e_ != hipSuccess) return hip_fail(e_, what); \
   } while (0)
 
-// qpb_solve_host (meq < 0) and qpb_solve_eq_host: copy in, solve, copy out
+// qpb_solve_host (meq < 0), qpb_solve_eq_host and qpb_solve_shared_host
+// (shared >= 0: a shared operand is one matrix): copy in, solve, copy out
 static int solve_host(const qpb_desc *d, int32_t meq, const double *H, const double *f, const double *A,
-                      const double *b, double *x, double *lam, uint32_t *active, int32_t *status, int32_t *iters) {
+                      const double *b, double *x, double *lam, uint32_t *active, int32_t *status, int32_t *iters,
+                      int32_t shared = -1) {
   if (d->batch == 0) return 0;
   int rc = check_device();
   if (rc) return rc;
   const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
   DevBuf dH, df, dA, db, dx, dl, da, ds, di;
-  HIPCHK(up(dH, H, B * n * n * 8), "H");
+  const size_t BH = (shared > 0 && (shared & QPB_SHARED_H)) ? 1 : B, BA = (shared > 0 && (shared & QPB_SHARED_A)) ? 1 : B;
+  HIPCHK(up(dH, H, BH * n * n * 8), "H");
   HIPCHK(up(df, f, B * n * 8), "f");
-  HIPCHK(up(dA, m ? A : nullptr, B * m * n * 8), "A");
+  HIPCHK(up(dA, m ? A : nullptr, BA * m * n * 8), "A");
   HIPCHK(up(db, m ? b : nullptr, B * m * 8), "b");
   HIPCHK(alloc(dx, x, B * n * 8), "x");
   HIPCHK(alloc(dl, m ? lam : nullptr, B * m * 8), "lam");
@@ -349,7 +478,11 @@ static int solve_host(const qpb_desc *d, int32_t meq, const double *H, const dou
   HIPCHK(alloc(di, iters, B * 4), "iters");
   rc = meq < 0 ? qpb_solve(d, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
                            (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr)
-               : qpb_solve_eq(d, meq, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
+       : shared >= 0
+           ? qpb_solve_shared(d, meq, shared, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p,
+                              (double *)dx.p, (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p,
+                              nullptr)
+           : qpb_solve_eq(d, meq, (double *)dH.p, (double *)df.p, (double *)dA.p, (double *)db.p, (double *)dx.p,
                               (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "qpb_solve_host kernel");
@@ -383,6 +516,29 @@ extern "C" int qpb_solve_eq_host(const qpb_desc *d, int32_t meq, const double *H
   return solve_host(d, meq, H, f, A, b, x, lam, active, status, iters);
 }
 
+extern "C" int qpb_solve_shared_host(const qpb_desc *d, int32_t meq, int32_t shared, const double *H,
+                                     const double *f, const double *A, const double *b, double *x, double *lam,
+                                     uint32_t *active, int32_t *status, int32_t *iters) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_shared(d, meq, shared);
+  if (rc) return rc;
+  shared = shared_of(d, shared);
+  if (shared == 0) return qpb_solve_eq_host(d, meq, H, f, A, b, x, lam, active, status, iters);
+  if (meq > d->m) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_shared: meq=%d > m=%d", meq, d->m);
+  if (d->batch > 0) {
+    rc = check_solve_arrays(d, H, f, A, b, x, lam, active, status);  // host pointers: the same rules
+    if (rc) return rc;
+  }
+  return solve_host(d, meq, H, f, A, b, x, lam, active, status, iters, shared);
+}
+
+// qpb_solve_backward_host and qpb_solve_shared_backward_host (shared > 0: a
+// shared operand and its gradient are one matrix): copy in, run, copy out
+static int backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
+                         const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
+                         double *gH, double *gf, double *gA, double *gb);
+
 extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const double *A, const double *x,
                                        const double *lam, const uint32_t *active, const int32_t *status,
                                        const double *gx, double *gH, double *gf, double *gA, double *gb) {
@@ -390,6 +546,26 @@ extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const
   if (rc) return rc;
   rc = check_bwd(d);
   if (rc) return rc;
+  return backward_host(d, 0, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+}
+
+extern "C" int qpb_solve_shared_backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A,
+                                              const double *x, const double *lam, const uint32_t *active,
+                                              const int32_t *status, const double *gx, double *gH, double *gf,
+                                              double *gA, double *gb) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_shared_bwd(d, shared);
+  if (rc) return rc;
+  shared = shared_of(d, shared);
+  if (shared == 0) return qpb_solve_backward_host(d, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+  return backward_host(d, shared, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+}
+
+static int backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
+                         const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
+                         double *gH, double *gf, double *gA, double *gb) {
+  int rc;
   if (d->batch == 0) return 0;
   rc = check_bwd_arrays(d, H, A, x, lam, active, gx, gH, gf, gA, gb);  // host pointers: the same rules
   if (rc) return rc;
@@ -397,25 +573,26 @@ extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const
   if (rc) return rc;
   const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
   DevBuf dH, dA, dx, dl, da, ds, dg, oH, of, oA, ob;
-  HIPCHK(up(dH, H, B * n * n * 8), "H");
-  HIPCHK(up(dA, m ? A : nullptr, B * m * n * 8), "A");
+  const size_t BH = (shared & QPB_SHARED_H) ? 1 : B, BA = (shared & QPB_SHARED_A) ? 1 : B;
+  HIPCHK(up(dH, H, BH * n * n * 8), "H");
+  HIPCHK(up(dA, m ? A : nullptr, BA * m * n * 8), "A");
   HIPCHK(up(dx, x, B * n * 8), "x");
   HIPCHK(up(dl, m ? lam : nullptr, B * m * 8), "lam");
   HIPCHK(up(da, m ? active : nullptr, B * w * 4), "active");
   HIPCHK(up(ds, status, B * 4), "status");
   HIPCHK(up(dg, gx, B * n * 8), "gx");
-  HIPCHK(alloc(oH, gH, B * n * n * 8), "gH");
+  HIPCHK(alloc(oH, gH, BH * n * n * 8), "gH");
   HIPCHK(alloc(of, gf, B * n * 8), "gf");
-  HIPCHK(alloc(oA, m ? gA : nullptr, B * m * n * 8), "gA");
+  HIPCHK(alloc(oA, m ? gA : nullptr, BA * m * n * 8), "gA");
   HIPCHK(alloc(ob, m ? gb : nullptr, B * m * 8), "gb");
-  rc = qpb_solve_backward(d, (double *)dH.p, (double *)dA.p, (double *)dx.p, (double *)dl.p, (uint32_t *)da.p,
-                          (int32_t *)ds.p, (double *)dg.p, (double *)oH.p, (double *)of.p, (double *)oA.p,
-                          (double *)ob.p, nullptr);
+  rc = qpb_solve_shared_backward(d, shared, (double *)dH.p, (double *)dA.p, (double *)dx.p, (double *)dl.p,
+                                 (uint32_t *)da.p, (int32_t *)ds.p, (double *)dg.p, (double *)oH.p, (double *)of.p,
+                                 (double *)oA.p, (double *)ob.p, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "qpb_solve_backward_host kernel");
-  HIPCHK(down(gH, oH, B * n * n * 8), "gH D2H");
+  HIPCHK(down(gH, oH, BH * n * n * 8), "gH D2H");
   HIPCHK(down(gf, of, B * n * 8), "gf D2H");
-  HIPCHK(down(m ? gA : nullptr, oA, B * m * n * 8), "gA D2H");
+  HIPCHK(down(m ? gA : nullptr, oA, BA * m * n * 8), "gA D2H");
   HIPCHK(down(m ? gb : nullptr, ob, B * m * 8), "gb D2H");
   return 0;
 }
@@ -594,4 +771,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics)"; }

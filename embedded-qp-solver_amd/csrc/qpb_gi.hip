@@ -86,14 +86,21 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 // A row that depends on the equalities before it is left out (bit clear,
 // lam = 0) when its residual is within the tolerance, else the QP is
 // INFEASIBLE.  The finish writes lam and x with the caller's signs.
-template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false>
+// SH (qpb_solve_shared): the QP strides of H and A, in doubles, are the
+// run-time strideH and strideA -- 0 for an operand the whole batch shares, or
+// n n and m n -- in every address that reads H or A; the arithmetic is the
+// other forms', so the outputs are theirs bit for bit.  Without SH the two
+// arguments are unused and every address is formed as before.
+template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
     uint32_t *__restrict__ actg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m,
     long long batch, int max_iter, double feas_tol, int flags, unsigned long long *__restrict__ dbg,
-    long long grp, [[maybe_unused]] int meq = 0) {
+    long long grp, [[maybe_unused]] int meq = 0, [[maybe_unused]] long long strideH = 0,
+    [[maybe_unused]] long long strideA = 0) {
   static_assert(!FULL || N16, "FULL implies n == 16");
+  static_assert(!SH || !STAMP, "the shared form has no stamped build");
   SectionClock<STAMP> clk;
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -130,9 +137,9 @@ __device__ __forceinline__ void gi_group(
   // (512 and 16384 are multiples of 4: the group's four indices never wrap,
   // the masked index of its first QP serves all of them)
   const long long gi0 = (flags & QPB_FLAG_DIAG_L2) ? (g0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (g0 & 16383) : g0;
-  const double *Hs = Hg + gi0 * (long long)n * n;
+  const double *Hs = SH ? Hg + gi0 * strideH : Hg + gi0 * (long long)n * n;
   // m == 0: A/b may be NULL -- point the (masked) row loads at H instead
-  const double *As = m > 0 ? Ag + gi0 * (long long)m * n : Hs;
+  const double *As = m > 0 ? (SH ? Ag + gi0 * strideA : Ag + gi0 * (long long)m * n) : Hs;
   const double *bs = m > 0 ? bg + gi0 * (long long)m : Hs;
   const uint32_t un = (uint32_t)n, umn = (uint32_t)m * un;
   double Lr[NL];  // row l of H, becomes row l of L
@@ -191,8 +198,8 @@ __device__ __forceinline__ void gi_group(
     // 2(l&7), 2(l&7)+1.  Rows reach their owner lane through a transpose in
     // this QP's LDS slot (free until the factorisation ends).
     const uint32_t hoff = (uint32_t)(hr * NL + hc) * 8u;  // row hr, column hc of a 16-column matrix
-    const double *Hl = &at_off<double>(Hs, sl * (NL * NL * 8u) + hoff);
-    const double *Al = &at_off<double>(As, sl * umn * 8u + hoff);
+    const double *Hl = &at_off<double>(Hs, (SH ? sl * ((uint32_t)strideH * 8u) : sl * (NL * NL * 8u)) + hoff);
+    const double *Al = &at_off<double>(As, (SH ? sl * ((uint32_t)strideA * 8u) : sl * umn * 8u) + hoff);
     double2 hv[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) hv[t] = *reinterpret_cast<const double2 *>(&Hl[2 * t * NL]);
@@ -232,7 +239,8 @@ __device__ __forceinline__ void gi_group(
     wave_lds_sync();
   } else {  // padded n < 16: clamped per-lane row loads, identity outside n
     const int lc = l < n ? l : n - 1;
-    const uint32_t hrow = (sl * un + (uint32_t)lc) * un * 8u;  // the lane's row of H
+    const uint32_t hrow =  // the lane's row of H
+        SH ? sl * (uint32_t)strideH * 8u + (uint32_t)lc * un * 8u : (sl * un + (uint32_t)lc) * un * 8u;
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       const double h = at_off<double>(Hs, hrow + (uint32_t)(j < n ? j : n - 1) * 8u);
@@ -243,7 +251,8 @@ __device__ __forceinline__ void gi_group(
       const int row = l + NL * r;
       const bool ok = row < m;
       const int rc = ok ? row : 0;
-      const uint32_t arow_off = (sl * umn + (uint32_t)rc * un) * 8u;
+      const uint32_t arow_off =
+          SH ? sl * (uint32_t)strideA * 8u + (uint32_t)rc * un * 8u : (sl * umn + (uint32_t)rc * un) * 8u;
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
         const double a = at_off<double>(As, arow_off + (uint32_t)(j < n ? j : n - 1) * 8u);
@@ -681,7 +690,8 @@ __device__ __forceinline__ void gi_group(
   const uint32_t slo = (uint32_t)(live_o ? slot_o : rem_o - 1);
   const long long gio0 =
       (flags & QPB_FLAG_DIAG_L2) ? (go0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (go0 & 16383) : go0;
-  const double *Aso = m > 0 ? Ag + gio0 * (long long)m * n : Hg + gio0 * (long long)n * n;
+  const double *Aso = SH ? (m > 0 ? Ag + gio0 * strideA : Hg + gio0 * strideH)
+                         : (m > 0 ? Ag + gio0 * (long long)m * n : Hg + gio0 * (long long)n * n);
   // The A-row loads go out first, in at most two groups of eight (one
   // wave-uniform test per group: a test per load made each load a branch
   // with its own wait); the work that does not need them -- the multipliers by
@@ -695,7 +705,8 @@ __device__ __forceinline__ void gi_group(
   const uint32_t iob = (uint32_t)(iam > 0 ? iam : 0) * (uint32_t)n * 8u;
   asm volatile("s_nop 1" ::"v"(iob));  // its DPP reads below may sit behind a branch only
   const int lc = l < n ? l : n - 1;
-  const uint32_t acol = (slo * (uint32_t)m * (uint32_t)n + (uint32_t)lc) * 8u;
+  const uint32_t acol = SH ? slo * ((uint32_t)strideA * 8u) + (uint32_t)lc * 8u
+                           : (slo * (uint32_t)m * (uint32_t)n + (uint32_t)lc) * 8u;
   double arow[NL];
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
@@ -809,6 +820,18 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_eq_kernel(
                                        feas_tol, 0, nullptr, blockIdx.x, meq);
 }
 
+// qpb_solve_shared's form: gi_group with SH, with or without equality rows
+template <int MR, bool N16, bool FULL, bool EQ, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_shared_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
+    const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
+    uint32_t *__restrict__ actg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, int meq,
+    long long batch, int max_iter, double feas_tol, long long strideH, long long strideA) {
+  __shared__ double lds[QPB * SLOT];
+  gi_group<MR, N16, FULL, false, EQ, true>(lds, Hg, fg, Ag, bg, xg, lamg, actg, statg, itg, n, m, batch, max_iter,
+                                           feas_tol, 0, nullptr, blockIdx.x, meq, strideH, strideA);
+}
+
 }  // namespace qpb
 
 // launcher used by qpb_api.hip
@@ -861,5 +884,26 @@ extern "C" hipError_t qpb_launch_gi_sections(const qpb_desc *d, const double *H,
   hipLaunchKernelGGL((qpb::gi_dense_kernel<2, true, false, true>), dim3((unsigned)blocks), dim3(64), 0, stream, H, f,
                      A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol, d->flags,
                      sections);
+  return hipGetLastError();
+}
+
+// qpb_solve_shared, n <= 16 and m <= 32: the six forms with run-time QP strides
+// of H and A (0: one copy for the batch), plain (meq == 0) and EQ
+extern "C" hipError_t qpb_launch_gi_shared(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                           const double *H, const double *f, const double *A, const double *b,
+                                           double *x, double *lam, uint32_t *active, int32_t *status, int32_t *iters,
+                                           hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    if (meq > 0)
+      hipLaunchKernelGGL((qpb::gi_dense_shared_kernel<MR(), N16(), FULL(), true, qpb::kEqOcc>),
+                         dim3((unsigned)blocks), dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n,
+                         d->m, meq, (long long)d->batch, max_iter, tol, strideH, strideA);
+    else
+      hipLaunchKernelGGL((qpb::gi_dense_shared_kernel<MR(), N16(), FULL(), false, 3>), dim3((unsigned)blocks),
+                         dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, 0,
+                         (long long)d->batch, max_iter, tol, strideH, strideA);
+  });
   return hipGetLastError();
 }

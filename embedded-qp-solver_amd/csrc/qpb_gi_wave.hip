@@ -89,14 +89,27 @@ __device__ __forceinline__ void dpp_ready2(double a, double b) { asm volatile("s
 // were (only the template argument list in their names grew).
 constexpr int kEqShift = 16;
 static_assert(QPB_MAX_M < (1 << kEqShift));
-template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false>
+// SH (qpb_solve_shared): H and / or A is one matrix for the whole batch, its QP
+// stride 0 instead of n n or m n.  Which, the QPB_SHARED_* bits, rides in `m`
+// as well, above meq: m | meq << kEqShift | shared << kShShift.  Every read of
+// H or A goes through the QP's two base pointers, so nothing else changes and
+// the outputs are the other forms' bit for bit.
+constexpr int kShShift = 28;
+static_assert((QPB_MAX_M << kEqShift) < (1 << kShShift) && (3 << kShShift) > 0);
+template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
     double feas_tol, unsigned long long *__restrict__ dbg = nullptr) {
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
+  static_assert(!SH || !(STAMP || REDO || BOX), "the shared form is the plain or the EQ kernel's");
   __shared__ double lds[SLOT];
+  [[maybe_unused]] int shared = 0;
+  if constexpr (SH) {
+    shared = m >> kShShift;
+    m &= (1 << kShShift) - 1;
+  }
   [[maybe_unused]] int meq = 0;
   if constexpr (EQ) {
     meq = m >> kEqShift;
@@ -114,9 +127,11 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double *xch = R;             // the exchange row: R's column 0, never read by the back substitution
   double *xsd = lds + OFF_X;   // s_p, |D[p,:]|^2
 
-  const double *Hq = Hg + g * (long long)n * n;
+  const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
   // BOX: Ag = lb, bg = ub (n per QP, either may be NULL), m = 2n
-  const double *Aq = BOX ? Hq : m > 0 ? Ag + g * (long long)m * n : Hq;
+  const double *Aq = BOX      ? Hq
+                     : m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n)
+                             : Hq;
   const double *bq = BOX ? Hq : m > 0 ? bg + g * (long long)m : Hq;
   const bool rowok = l < m;
 
@@ -800,4 +815,24 @@ extern "C" hipError_t qpb_launch_gi_wave_box(const qpb_desc *d, const double *H,
                                              const double *ub, double *x, double *lam, uint32_t *active,
                                              int32_t *status, int32_t *iters, hipStream_t stream) {
   return launch_gi_wave<3, false, false, true>(d, H, f, lb, ub, x, lam, active, status, iters, stream);
+}
+
+// qpb_solve_shared for the n <= 32, m <= 64 class: a QP stride of 0 (one copy
+// for the batch) or the batched one for each of H and A, plain (meq == 0) or EQ
+extern "C" hipError_t qpb_launch_gi_wave_shared(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                                const double *H, const double *f, const double *A, const double *b,
+                                                double *x, double *lam, uint32_t *active, int32_t *status,
+                                                int32_t *iters, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | (strideA == 0 ? QPB_SHARED_A : 0);
+  const int mm = d->m | (meq << qpb::wv::kEqShift) | (shared << qpb::wv::kShShift);
+  if (meq > 0)
+    hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, true>), dim3((unsigned)d->batch),
+                       dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n, mm, (long long)d->batch,
+                       max_iter, tol, nullptr);
+  else
+    hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, false, true>), dim3((unsigned)d->batch),
+                       dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n, mm, (long long)d->batch,
+                       max_iter, tol, nullptr);
+  return hipGetLastError();
 }

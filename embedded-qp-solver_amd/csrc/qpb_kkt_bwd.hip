@@ -64,13 +64,22 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
 // MR: rows of A per lane (m <= 16 MR).  N16: n == 16 (coalesced loads and
 // stores through this QP's LDS slot); otherwise the rows are padded with the
 // identity and padded variables take no part.
-template <int MR, bool N16>
+// SH (pass 1 of qpb_solve_shared_backward): H and / or A is one matrix for the
+// whole batch, its QP stride 0; the QPB_SHARED_* bits ride in `m`, at kShShift.
+constexpr int kShShift = 28;
+static_assert(QPB_MAX_M < (1 << kShShift) && (3 << kShShift) > 0);
+template <int MR, bool N16, bool SH = false>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
     const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
     double *__restrict__ gbg, int n, int m, long long batch) {
   __shared__ double lds[QPB * SLOT];
+  [[maybe_unused]] int shared = 0;
+  if constexpr (SH) {
+    shared = m >> kShShift;
+    m &= (1 << kShShift) - 1;
+  }
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
   const long long g = ragged_qp(blockIdx.x, slot, batch).g;
@@ -83,8 +92,10 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   // ------------------------------------------------------------------ load
   const bool var = N16 || l < n;
   const int lc = var ? l : n - 1;
-  const double *Hq = Hg + g * (long long)n * n;
-  const double *Aq = m > 0 ? Ag + g * (long long)m * n : Hq;  // m == 0: the (masked) row loads read H
+  const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
+  // m == 0: the (masked) row loads read H
+  const double *Aq =
+      m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n) : Hq;
   const bool ok = statg ? statg[g] == QPB_OK : true;
   // a QP that is not QPB_OK takes no trips and stores zeros
   uint32_t W = (m > 0 && ok) ? actg[g] : 0u;
@@ -406,6 +417,7 @@ __device__ __forceinline__ double wave_sum(double t) {
   return (readlane_d(t, 0) + readlane_d(t, 16)) + (readlane_d(t, 32) + readlane_d(t, 48));
 }
 
+template <bool SH = false>
 __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
@@ -415,14 +427,19 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
   __shared__ double colk[W_COL];
+  [[maybe_unused]] int shared = 0;
+  if constexpr (SH) {
+    shared = m >> kShShift;
+    m &= (1 << kShShift) - 1;
+  }
   const int lane = threadIdx.x;
   const int i = lane & (WN - 1), half = lane >> 5;
   const bool low = lane < WN;      // the lanes that carry a component
   const long long g = blockIdx.x;  // one workgroup of one wave per QP: always < batch
   double *Lm = lds + W_L, *Qm = lds + W_Q;
   double *vb = lds + W_V, *cb = lds + W_C, *ub = lds + W_U, *ir = lds + W_IR, *posb = lds + W_POS;
-  const double *Hq = Hg + g * (long long)n * n;
-  const double *Aq = Ag + g * (long long)m * n;
+  const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
+  const double *Aq = SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n;
   const bool ok = statg ? statg[g] == QPB_OK : true;
   // the active mask as one 64-bit word (wave-uniform); a QP that is not QPB_OK takes no trips
   const int words = (m + 31) / 32;
@@ -604,7 +621,7 @@ extern "C" hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, con
                                          const double *gx, double *gH, double *gf, double *gA, double *gb,
                                          hipStream_t stream) {
   if (d->n > 16 || d->m > 32) {  // one workgroup of one wave per QP
-    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x, lam,
+    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x, lam,
                        active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch);
     return hipGetLastError();
   }
@@ -612,6 +629,28 @@ extern "C" hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, con
   qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {  // (no FULL form)
     hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16()>), dim3((unsigned)blocks), dim3(64), 0, stream, H,
                        A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch);
+  });
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_shared_backward: the SH forms, a QP stride of 0 (one copy
+// for the batch) or the batched one for each of H and A; gH / gA are NULL where
+// pass 2 (qpb_kkt_bwd_sum.hip) sums the gradient
+extern "C" hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long strideH, long long strideA,
+                                                const double *H, const double *A, const double *x, const double *lam,
+                                                const uint32_t *active, const int32_t *status, const double *gx,
+                                                double *gH, double *gf, double *gA, double *gb, hipStream_t stream) {
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | (strideA == 0 ? QPB_SHARED_A : 0);
+  const int mm = d->m | (shared << qpb::bwd::kShShift);
+  if (d->n > 16 || d->m > 32) {
+    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<true>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x,
+                       lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), true>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch);
   });
   return hipGetLastError();
 }

@@ -41,6 +41,27 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, c
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H, const double *x,
                                                const uint32_t *active, const int32_t *status, const double *gx,
                                                double *gH, double *gf, double *glb, double *gub, hipStream_t stream);
+// qpb_solve_shared: H and A with run-time QP strides in doubles (0: one copy for
+// the whole batch, else n n and m n); meq == 0 is the plain form, meq > 0 the EQ form
+typedef hipError_t qpb_gi_shared_launcher(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                          const double *H, const double *f, const double *A, const double *b,
+                                          double *x, double *lam, uint32_t *active, int32_t *status, int32_t *iters,
+                                          hipStream_t stream);
+QPB_LAUNCHER qpb_gi_shared_launcher qpb_launch_gi_shared,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_shared;                             // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_shared_backward, pass 1: qpb_launch_kkt_bwd with the same strides
+// (gH / gA NULL where pass 2 sums the gradient)
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long strideH, long long strideA,
+                                                  const double *H, const double *A, const double *x,
+                                                  const double *lam, const uint32_t *active, const int32_t *status,
+                                                  const double *gx, double *gH, double *gf, double *gA, double *gb,
+                                                  hipStream_t stream);
+// ... pass 2 (qpb_kkt_bwd_sum.hip): the n x n and / or m x n sums over the whole
+// batch from pass 1's gf (dx) and gb; slots: qpb::sum_plan(batch).slots times
+// qpb::sum_slot_doubles(n, m) doubles of scratch
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_sum(const qpb_desc *d, const double *x, const double *dx, const double *gb,
+                                               const double *lam, const uint32_t *active, const int32_t *status,
+                                               double *slots, double *gH, double *gA, hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

@@ -126,6 +126,72 @@ static_assert(route_bwd_box(kBwdBoxMaxN).step > 0 && route_bwd_box(kBwdBoxMaxN +
 static_assert(route_bwd_box(16).kernel == route(16, 32, 0, true).kernel &&
               route_bwd_box(17).kernel == route(17, 34, 0, true).kernel);
 
+// qpb_solve_shared with a shared H or A (and any meq): route_eq, the SH forms
+// of the two wavefront-level classes; above them -- the Gram class -- there is
+// no shared form yet: step 0, and the call is unsupported.
+constexpr Route route_shared(int n, int m) {
+  const Route r = route_eq(n, m);
+  return {r.kernel, r.step};
+}
+// qpb_solve_shared_backward with a shared H or A: route_bwd in the same way
+constexpr Route route_shared_bwd(int n, int m) {
+  const Route r = route_bwd(n, m);
+  return {r.kernel, r.step};
+}
+constexpr int kSharedMaxN = 32, kSharedMaxM = 64;  // the limit the two routes' step 0 stands for
+
+static_assert(route_shared(16, 32).kernel == Kernel::gi_dense && route_shared(1, 0).kernel == Kernel::gi_dense);
+static_assert(route_shared(16, 33).kernel == Kernel::gi_wave && route_shared(32, 64).kernel == Kernel::gi_wave);
+static_assert(route_shared(16, 32).step == 1LL << 27 && route_shared(32, 64).step == 1LL << 25);
+static_assert(route_shared(33, 0).step == 0 && route_shared(32, 65).step == 0 && route_shared(128, 256).step == 0);
+static_assert(route_shared_bwd(16, 32).kernel == Kernel::gi_dense && route_shared_bwd(17, 0).kernel == Kernel::gi_wave);
+static_assert(route_shared_bwd(16, 32).step == 1LL << 27 && route_shared_bwd(32, 64).step == 1LL << 25);
+static_assert(route_shared_bwd(33, 0).step == 0 && route_shared_bwd(32, 65).step == 0);
+static_assert(route_shared(kSharedMaxN, kSharedMaxM).step > 0 && route_shared(kSharedMaxN + 1, 1).step == 0 &&
+              route_shared(1, kSharedMaxM + 1).step == 0);
+static_assert(route_shared_bwd(kSharedMaxN, kSharedMaxM).step > 0 && route_shared_bwd(kSharedMaxN + 1, 1).step == 0 &&
+              route_shared_bwd(1, kSharedMaxM + 1).step == 0);
+
+// The slice plan of the batch sum (qpb_kkt_bwd_sum.hip): `slots` consecutive
+// slices of `per` QPs, the last one shorter; one wavefront and one workspace
+// slot per slice.  A function of the batch size alone -- not of the device --
+// so that the summed gradients' bits are reproducible anywhere.  per is a
+// multiple of 4 (a wave takes 4 QPs per matrix-core step), at least
+// kSumMinSlice (a shorter slice leaves the finish kernel more slots to add
+// than the wave saved), and large enough for at most kSumMaxSlots slices
+// (four waves on each of 256 CUs; the slots are the finish kernel's input).
+struct SumPlan {
+  long long slots;  // slices, each with a slot of sum_slot_doubles(n, m) doubles
+  long long per;    // QPs per slice
+};
+constexpr long long kSumMaxSlots = 1024, kSumMinSlice = 128;
+constexpr SumPlan sum_plan(long long batch) {
+  if (batch <= 0) return {0, 0};
+  long long per = (batch + kSumMaxSlots - 1) / kSumMaxSlots;
+  if (per < kSumMinSlice) per = kSumMinSlice;
+  per = (per + 3) / 4 * 4;
+  return {(batch + per - 1) / per, per};
+}
+// a slot: S as 16 ceil(n/16) squared, then gA's sum as 16 ceil(m/16) x 16 ceil(n/16)
+constexpr long long sum_slot_doubles(int n, int m) {
+  const long long nt = (n + 15) / 16, mt = (m + 15) / 16;
+  return 256 * (nt * nt + mt * nt);
+}
+
+static_assert(kSumMinSlice % 4 == 0 && kSumMinSlice > 0 && kSumMaxSlots > 0);
+static_assert(sum_plan(0).slots == 0 && sum_plan(1).slots == 1 && sum_plan(1).per == kSumMinSlice);
+static_assert(sum_plan(kSumMinSlice).slots == 1 && sum_plan(kSumMinSlice + 1).slots == 2);
+static_assert(sum_plan(kSumMaxSlots * kSumMinSlice).slots == kSumMaxSlots &&
+              sum_plan(kSumMaxSlots * kSumMinSlice).per == kSumMinSlice);
+static_assert(sum_plan(kSumMaxSlots * kSumMinSlice + 1).slots <= kSumMaxSlots &&
+              sum_plan(kSumMaxSlots * kSumMinSlice + 1).per == kSumMinSlice + 4);
+static_assert(sum_plan(1LL << 20).slots == 1024 && sum_plan(1LL << 20).per == 1024);
+static_assert(sum_plan(1LL << 40).slots <= kSumMaxSlots && sum_plan(1LL << 40).per % 4 == 0 &&
+              sum_plan(1LL << 40).slots * sum_plan(1LL << 40).per >= 1LL << 40 &&
+              (sum_plan(1LL << 40).slots - 1) * sum_plan(1LL << 40).per < 1LL << 40);
+static_assert(sum_slot_doubles(16, 32) == 768 && sum_slot_doubles(32, 64) == 3072 && sum_slot_doubles(1, 0) == 256 &&
+              sum_slot_doubles(17, 33) == 256 * (4 + 6));
+
 // One array of a batched call: per_qp elements per QP from base.  Only an
 // optional array may be NULL, and then it is NULL in every chunk.
 template <class T>

@@ -13,6 +13,8 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve(H, f)                -> qpb_solve, m=0  (test/qp_ref.py:35 semantics)
     solve_eq(H, f, A, b, meq)  -> qpb_solve_eq    (rows 0 .. meq-1 of A are equalities)
     solve_backward(H, A, sol, gx) -> qpb_solve_backward (gradients of a solve; autograd: qpb.diff)
+    solve_shared(H, f, A, b, meq) -> qpb_solve_shared (a 2-D H and / or A: one matrix for the whole batch)
+    solve_shared_backward(H, A, sol, gx) -> qpb_solve_shared_backward (a shared operand's gradient summed over the batch)
     solve_box_backward(H, sol, gx) -> qpb_solve_box_backward (gradients of a box solve, n <= 32)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
@@ -47,6 +49,8 @@ REF_MAX_N = 1024  # qpb_ref_solve / qpb_matrix_invert (QPB_REF_MAX_N)
 # qpb_desc.flags (include/qpb.h)
 FLAG_DIAG_L2, FLAG_DIAG_MALL = 1, 16
 FLAG_MIXED, FLAG_DIAG_NO_REDO = 32, 64
+# the `shared` argument of qpb_solve_shared / qpb_solve_shared_backward
+SHARED_H, SHARED_A = 1, 2
 FLAG_DIAG_WAVE = 256  # n <= 16 solved by the one-QP-per-wavefront kernel (lockstep endpoint; measurement only)
 STATUS_REDO = 100  # internal: a QP the mixed kernel leaves to the fp64 re-solve (FLAG_DIAG_NO_REDO only)
 
@@ -75,6 +79,14 @@ _lib.qpb_solve_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 12
 _lib.qpb_solve_backward.restype = ctypes.c_int
 _lib.qpb_solve_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
 _lib.qpb_solve_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_shared.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 10
+_lib.qpb_solve_shared.restype = ctypes.c_int
+_lib.qpb_solve_shared_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 9
+_lib.qpb_solve_shared_host.restype = ctypes.c_int
+_lib.qpb_solve_shared_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 12
+_lib.qpb_solve_shared_backward.restype = ctypes.c_int
+_lib.qpb_solve_shared_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
+_lib.qpb_solve_shared_backward_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
 _lib.qpb_solve_box_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
@@ -350,6 +362,154 @@ def solve_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
     _check(rc, "qpb_solve_backward_host")
     return gH, gf, gA, gb
 
+
+def _shared_shape(who: str, H, f, A, b):
+    """(B, n, m, shared) of a call whose H and / or A may be 2-D, one matrix for
+    the whole batch: contiguous float64 CUDA tensors on one device."""
+    import torch
+    if not (H.is_cuda and f.is_cuda):
+        raise ValueError(f"{who} expects CUDA (HIP) tensors; use the _host form for numpy")
+    B, n = f.shape
+    m = 0 if A is None else A.shape[-2]
+    for t in (H, f) + ((A, b) if m else ()):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+        if t.device != f.device:
+            raise ValueError("the inputs must live on the same CUDA device")
+    shared = (SHARED_H if H.dim() == 2 else 0) | (SHARED_A if m and A.dim() == 2 else 0)
+    if tuple(H.shape) not in ((n, n), (B, n, n)) or (m and (tuple(A.shape) not in ((m, n), (B, m, n))
+                                                            or tuple(b.shape) != (B, m))):
+        raise ValueError("shape mismatch")
+    return B, n, m, shared
+
+
+def solve_shared(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                 out: Solution | None = None, stream=None) -> Solution:
+    """``solve_eq`` with one H and / or one A for the whole batch (qpb_solve_shared).
+
+    A 2-D ``H`` (n, n) is shared by all B QPs and read from that one copy; a
+    3-D ``H`` (B, n, n) is batched as in ``solve``.  The same holds for ``A``
+    (m, n) or (B, m, n).  f (B, n) and b (B, m) are per QP.  Every output is
+    bit for bit what ``solve_eq`` gives on expanded copies.  With a shared
+    operand n <= 32 and m <= 64."""
+    B, n, m, shared = _shared_shape("qpb.solve_shared", H, f, A, b)
+    if out is None:
+        out = _empty_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_shared(ctypes.byref(d), int(meq), shared, _ptr(H), _ptr(f), _ptr(A) if m else None,
+                               _ptr(b) if m else None, _ptr(out.x), _ptr(out.lam), _ptr(out.active),
+                               _ptr(out.status), _ptr(out.iters), _stream_ptr(stream))
+    _check(rc, "qpb_solve_shared")
+    return out
+
+
+def solve_shared_host(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0) -> Solution:
+    """numpy in / numpy out (qpb_solve_shared_host): ``solve_shared`` with host arrays."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    B, n = f.shape
+    m = 0 if A is None else A.shape[-2]
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if m and A.ndim == 2 else 0)
+    if H.shape not in ((n, n), (B, n, n)) or (m and (A.shape not in ((m, n), (B, m, n)) or b.shape != (B, m))):
+        raise ValueError("shape mismatch")
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, (m + 31) // 32), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_shared_host(ctypes.byref(d), int(meq), shared, p(H), p(f), p(A) if m else None,
+                                    p(b) if m else None, p(x), p(lam), p(act), p(st), p(it))
+    _check(rc, "qpb_solve_shared_host")
+    return Solution(x, lam, act, st, it)
+
+
+def solve_shared_backward(H, A, sol: Solution, gx, *, need=NEED_ALL, stream=None):
+    """``solve_backward`` with one H and / or one A for the whole batch
+    (qpb_solve_shared_backward): a 2-D ``H`` (n, n) or ``A`` (m, n) is shared, and
+    its gradient comes back as ONE matrix of that shape, the sum over the batch
+    (QPs whose status is not OK contribute exactly 0); no (B, n, n) or
+    (B, m, n) tensor is allocated for it.  gf (B, n), gb (B, m) and the
+    gradient of a 3-D operand are ``solve_backward``'s bit for bit.  The sums
+    use the stream's cached workspace (``release_stream_workspace``).  With a
+    shared operand n <= 32 and m <= 64."""
+    import torch
+    B, n, m, shared = _shared_shape("qpb.solve_shared_backward", H, gx, A, None if A is None else sol.lam)
+    need = _need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if m and (not sol.active.is_contiguous() or sol.active.shape != (B, (m + 31) // 32)
+              or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(m/32)) tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(*H.shape) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    gA = new(*A.shape) if m and "A" in need else None
+    gb = new(B, m) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None  # m == 0 and only A / b wanted
+    d = Desc(n, m, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_shared_backward(ctypes.byref(d), shared, _ptr(H), _ptr(A) if m else None, _ptr(sol.x),
+                                        _ptr(sol.lam) if m else None, _ptr(sol.active) if m else None,
+                                        _ptr(sol.status), _ptr(gx), _ptr(gH), _ptr(gf), _ptr(gA), _ptr(gb),
+                                        _stream_ptr(stream))
+    _check(rc, "qpb_solve_shared_backward")
+    return gH, gf, gA, gb
+
+
+def solve_shared_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
+    """numpy in / numpy out (qpb_solve_shared_backward_host): ``solve_shared_backward`` with host arrays."""
+    import numpy as np
+    need = _need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    m = 0 if A is None else A.shape[-2]
+    lam = act = None
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        lam = np.ascontiguousarray(sol.lam, dtype=np.float64)
+        act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if m and A.ndim == 2 else 0)
+    if H.shape not in ((n, n), (B, n, n)) or x.shape != (B, n) or (m and A.shape not in ((m, n), (B, m, n))):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros(H.shape) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    gA = np.zeros(A.shape) if m and "A" in need else None
+    gb = np.zeros((B, m)) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None
+    d = Desc(n, m, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_shared_backward_host(ctypes.byref(d), shared, p(H), p(A), p(x), p(lam), p(act), p(st), p(gx),
+                                             p(gH), p(gf), p(gA), p(gb))
+    _check(rc, "qpb_solve_shared_backward_host")
+    return gH, gf, gA, gb
+
+
+def sum_plan(batch: int):
+    """(slots, QPs per slot) of the batch sum of ``solve_shared_backward``: the
+    slice plan of csrc/qpb_route.h (qpb::sum_plan), a function of the batch size
+    alone; tests/test_shared_plan.py holds the two together."""
+    if batch <= 0:
+        return 0, 0
+    per = max((batch + SUM_MAX_SLOTS - 1) // SUM_MAX_SLOTS, SUM_MIN_SLICE)
+    per = (per + 3) // 4 * 4
+    return (batch + per - 1) // per, per
+
+
+SUM_MAX_SLOTS, SUM_MIN_SLICE = 1024, 128  # kSumMaxSlots, kSumMinSlice
 
 BOX_NEED_ALL = ("H", "f", "lb", "ub")
 

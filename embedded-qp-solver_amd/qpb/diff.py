@@ -9,6 +9,11 @@ solution's active set, on the GPU).  This module imports torch at the top;
     loss = (w * x).sum()
     loss.backward()                                 # H.grad, f.grad, A.grad, b.grad
 
+A 2-D ``H`` (n, n) and / or ``A`` (m, n) is ONE matrix for the whole batch --
+the weights of a QP layer, with f and b from the network's input: the solve is
+``qpb.solve_shared``, the backward ``qpb.solve_shared_backward``, ``H.grad``
+is (n, n), and no (B, n, n) or (B, m, n) tensor is ever allocated.
+
 ``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
 and ub (``qpb.solve_box_backward``, n <= 32).
 """
@@ -27,8 +32,12 @@ class QPFunction(torch.autograd.Function):
         H, f = H.contiguous(), f.contiguous()
         if A is not None:
             A, b = A.contiguous(), b.contiguous()
-        sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol) if A is not None \
-            else qpb.solve(H, f, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.shared = H.dim() == 2 or (A is not None and A.dim() == 2)
+        if ctx.shared:
+            sol = qpb.solve_shared(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
+        else:
+            sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol) if A is not None \
+                else qpb.solve(H, f, max_iter=max_iter, feas_tol=feas_tol)
         ctx.has_rows = A is not None
         ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.status)
         ctx.mark_non_differentiable(sol.status)
@@ -42,7 +51,8 @@ class QPFunction(torch.autograd.Function):
             return (None,) * 7
         sol = qpb.Solution(x, lam, active, status, None)
         # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
-        gH, gf, gA, gb = qpb.solve_backward(H, A, sol, gx.contiguous(), need=wanted)
+        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
+        gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
         return gH, gf, gA, gb, None, None, None
 
 
@@ -91,5 +101,7 @@ def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: fl
     QP) is not differentiable.  QPs whose status is not OK contribute zero
     gradients.  The gradient is the derivative at fixed active set (qpb.h).
     The forward solves every shape ``qpb.solve_eq`` does; the backward needs
-    n <= 32 and m <= 64."""
+    n <= 32 and m <= 64.  H (n, n) and / or A (m, n) may be 2-D: one matrix
+    shared by the batch (n <= 32, m <= 64), whose gradient is the sum over the
+    batch, computed without a per-QP copy."""
     return QPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol))

@@ -14,6 +14,7 @@
  *   ... with equality rows, solve_qp(P, q, G, h, A, b)    qpb_solve_eq
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
+ *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -294,6 +295,97 @@ int qpb_solve_backward_host(const qpb_desc *desc, const double *H,
 			    const double *lam, const uint32_t *active,
 			    const int32_t *status, const double *gx, double *gH,
 			    double *gf, double *gA, double *gb);
+
+/* One H and / or one A for the whole batch: the condensed plant model of an MPC
+ * loop, or the learned weights of a QP layer, with f and b per QP.  `shared` is
+ * a combination of the two bits; a shared operand is ONE matrix, read from one
+ * copy (its QP stride is 0), the other is batched as everywhere else.  f, b and
+ * every output are per QP in qpb_solve's layouts. */
+#define QPB_SHARED_H 1 /* H is ONE n x n matrix for the whole batch */
+#define QPB_SHARED_A 2 /* A is ONE m x n matrix for the whole batch */
+
+/* qpb_solve_eq with a shared H and / or A.  Every output of every QP equals,
+ * bit for bit, what qpb_solve_eq writes for that QP on materialised copies of
+ * the shared operands: for every status of the contract above, and for NaN and
+ * +-Inf inputs as well (the kernels are qpb_solve_eq's with other addresses:
+ * the SH forms of qpb_gi.hip and qpb_gi_wave.hip; H is factored per QP).
+ *   shared == 0     the call is qpb_solve_eq, with all its rules.
+ *   m == 0          QPB_SHARED_A is ignored.
+ * Errors, in order: the descriptor as qpb_solve; meq < 0, desc->flags != 0, a
+ * bit of `shared` outside QPB_SHARED_H | QPB_SHARED_A, each
+ * QPB_ERR_INVALID_ARG; with a shared operand, n > 32 or m > 64
+ * QPB_ERR_UNSUPPORTED (with none, qpb_solve_eq's limit: meq > 0 above that
+ * size); meq > m QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers
+ * are looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
+ * with m <= 64.  Follow-ups: the n <= 128 Gram class (qpb_gi_gram.hip) has no
+ * shared form; a shared-H qpb_solve_box; and factoring a shared H ONCE -- with
+ * one H, L is the same for every QP and with one A so is D = A L^-T, which
+ * this version recomputes per QP on purpose, so that bit-for-bit equality with
+ * qpb_solve_eq is its test.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_shared(const qpb_desc *desc, int32_t meq, int32_t shared,
+		     const double *H, const double *f, const double *A,
+		     const double *b, double *x, double *lam, uint32_t *active,
+		     int32_t *status, int32_t *iters, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (a shared operand is one matrix). */
+int qpb_solve_shared_host(const qpb_desc *desc, int32_t meq, int32_t shared,
+			  const double *H, const double *f, const double *A,
+			  const double *b, double *x, double *lam,
+			  uint32_t *active, int32_t *status, int32_t *iters);
+
+/* qpb_solve_backward with a shared H and / or A: the gradient of a shared
+ * operand is ONE matrix, the sum over the batch.
+ *   gf (B x n), gb (B x m)   qpb_solve_backward's, bit for bit.
+ *   batched operand          its gradient is per QP (B x n x n, B x m x n),
+ *                            qpb_solve_backward's bit for bit.
+ *   shared H                 gH is n x n: 1/2 sum_k (dx_k x_k^T + x_k dx_k^T),
+ *                            symmetric bit for bit.
+ *   shared A                 gA is m x n: sum_k over the rows i in W_k of
+ *                            (dlam_ki x_k^T + lam_ki dx_k^T).
+ * A QP whose status is not QPB_OK contributes exactly 0 to a sum, even where
+ * its x or lam holds NaN; lam outside W is ignored, whatever it holds.
+ * Two passes: qpb_solve_backward's kernels without the summed gradients'
+ * stores, then the sums on the fp64 matrix cores (qpb_kkt_bwd_sum.hip): one
+ * wavefront per slice of the batch into its own slot of a workspace, and a
+ * second kernel that adds the slots in order.  The slices are a function of
+ * `batch` alone and there are no floating-point atomics: a summed output's
+ * bits depend on the inputs and on (n, m, batch) only -- not on the stream, on
+ * the state of the workspace cache or on the device's CU count.  They differ
+ * from a sum of qpb_solve_backward's per-QP outputs by rounding (the order of
+ * the additions) only.
+ *   shared == 0     the call is qpb_solve_backward, with all its rules.
+ *   m == 0          QPB_SHARED_A is ignored.
+ *   gH, gf, gA, gb  each may be NULL, as in qpb_solve_backward.
+ *   workspace       a summed gradient takes the per-(device, stream) scratch
+ *                   buffer (qpb_release_workspaces): at most 1024 slots of
+ *                   256 (ceil(n/16) + ceil(m/16)) ceil(n/16) doubles (24 MiB at
+ *                   n = 32, m = 64 from 131 072 QPs on), plus B n doubles for
+ *                   dx when gf is NULL, plus B m doubles for dlam when a
+ *                   summed gA is wanted and gb is NULL.  It is retained, as the
+ *                   other kernels' scratch is.
+ * Errors, in order: the descriptor as qpb_solve; flags != 0 and a bit of
+ * `shared` outside QPB_SHARED_H | QPB_SHARED_A QPB_ERR_INVALID_ARG; n > 32 or
+ * m > 64 QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are
+ * looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits and follow-ups as qpb_solve_shared.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_shared_backward(const qpb_desc *desc, int32_t shared,
+			      const double *H, const double *A, const double *x,
+			      const double *lam, const uint32_t *active,
+			      const int32_t *status, const double *gx, double *gH,
+			      double *gf, double *gA, double *gb, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (a shared operand and its
+ * gradient are one matrix). */
+int qpb_solve_shared_backward_host(const qpb_desc *desc, int32_t shared,
+				   const double *H, const double *A,
+				   const double *x, const double *lam,
+				   const uint32_t *active,
+				   const int32_t *status, const double *gx,
+				   double *gH, double *gf, double *gA,
+				   double *gb);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
