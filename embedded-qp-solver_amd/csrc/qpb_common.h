@@ -140,6 +140,20 @@ struct EqState<true> {
   bool pneg = false;  // per lane: the row at this active position was negated
 };
 
+// The state the RG kernel forms (qpb_solve_range) add beside EqState<true>: MR
+// rows per lane, each with two sides bl <= a x <= bu of which the lane holds
+// one at a time; empty in the other forms.
+template <bool RG, int MR>
+struct RgState {};
+template <int MR>
+struct RgState<true, MR> {
+  double lo[MR];       // bl as loaded (the set-up only)
+  double w[MR];        // bu - bl, +inf when a side is absent: the other side's slack is w - s
+  bool low[MR];        // the lane's row of D and its slack are the negated, lower-side ones
+  bool fresh = false;  // this trip's row p was selected in this trip (its side may change)
+  bool plow = false;   // row p is held lower-oriented
+};
+
 constexpr double kBig = 1.7976931348623157e308;  // DBL_MAX: the "no candidate" key
 
 // The multiplier an inequality's active position is written with.  In exact

@@ -91,15 +91,30 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 // n n and m n -- in every address that reads H or A; the arithmetic is the
 // other forms', so the outputs are theirs bit for bit.  Without SH the two
 // arguments are unused and every address is formed as before.
-template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false>
+// RG (qpb_solve_range, on EQ and SH): rows meq .. m-1 are two-sided,
+// bl <= a x <= bu, with bg = bu and blg = bl (either may be NULL: that side is
+// absent everywhere).  Only one side of a row can be active, so the lane holds
+// one side at a time: a bit per row says that its row of D and its slack are
+// the negated, lower-side ones (s = a x - bl), and w = bu - bl turns one
+// side's slack into the other's, w - s.  A row is selected on the side that
+// is violated; if that is not the side held, the owner negates the row and
+// its slack in place first -- what the EQ phase does for s_p > 0.  The active
+// position remembers the side (pneg travels with um and iam through a DROP),
+// the multiplier changes sign once at the end, and `lowg` gets the rows
+// active at their lower bound.  The norms (thr, ddr, fn2) do not depend on
+// the side.  A dropped row keeps its side; its slack follows the updates like
+// any inactive row's, and it can come back on either side.
+template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
     uint32_t *__restrict__ actg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m,
     long long batch, int max_iter, double feas_tol, int flags, unsigned long long *__restrict__ dbg,
     long long grp, [[maybe_unused]] int meq = 0, [[maybe_unused]] long long strideH = 0,
-    [[maybe_unused]] long long strideA = 0) {
+    [[maybe_unused]] long long strideA = 0, [[maybe_unused]] const double *__restrict__ blg = nullptr,
+    [[maybe_unused]] uint32_t *__restrict__ lowg = nullptr) {
   static_assert(!FULL || N16, "FULL implies n == 16");
+  static_assert(!RG || (EQ && SH), "the range form is built on the EQ and the shared forms");
   static_assert(!SH || !STAMP, "the shared form has no stamped build");
   SectionClock<STAMP> clk;
   const int l = threadIdx.x & (NL - 1);
@@ -151,9 +166,21 @@ __device__ __forceinline__ void gi_group(
   bool infeasible_row = false;
   // b and f with the matrices (same round trip)
   double bv[MR];
+  [[maybe_unused]] RgState<RG, MR> rg;
+  if constexpr (RG) {
+    // bu and bl, each NULL (wave-uniform) when no row has that side
+    const double *lo_s = blg ? blg + gi0 * (long long)m : nullptr;
 #pragma unroll
-  for (int r = 0; r < MR; ++r)
-    bv[r] = at_off<double>(bs, (sl * (uint32_t)m + (uint32_t)((FULL || l + NL * r < m) ? l + NL * r : 0)) * 8u);
+    for (int r = 0; r < MR; ++r) {
+      const uint32_t off = (sl * (uint32_t)m + (uint32_t)((FULL || l + NL * r < m) ? l + NL * r : 0)) * 8u;
+      bv[r] = bg ? at_off<double>(bs, off) : kInf;
+      rg.lo[r] = lo_s ? at_off<double>(lo_s, off) : -kInf;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < MR; ++r)
+      bv[r] = at_off<double>(bs, (sl * (uint32_t)m + (uint32_t)((FULL || l + NL * r < m) ? l + NL * r : 0)) * 8u);
+  }
   const double fv = at_off<double>(fg + gi0 * n, (sl * un + (uint32_t)(l < n ? l : n - 1)) * 8u);
   const double fl = (N16 || l < n) ? fv : 0.0;
   [[maybe_unused]] const int hr = l >> 3, hc = 2 * (l & 7);
@@ -179,6 +206,38 @@ __device__ __forceinline__ void gi_group(
   auto row_norms = [&](int r, const double (&row)[NL]) {
     const double nrm2 = dot2<NL>([&](int j) { return row[j]; }, [&](int j) { return row[j]; });
     const bool ok = FULL || l + NL * r < m;
+    if constexpr (RG) {
+      // A non-finite bound is an absent side (a NaN, and +-inf of either sign:
+      // in the pair form a row with b = -inf is never violated either).  A row
+      // whose only bound is the lower one is held lower-oriented from here on
+      // (w - s would be inf - inf).  One threshold for both sides, with the
+      // larger finite |bound|; crossed bounds beyond it and a zero row with 0
+      // outside [bl, bu] end the QP as QPB_INFEASIBLE before the loop.  The
+      // lower bound of an equality is not looked at.
+      const bool eqr = ok && l + NL * r < meq;
+      const bool has_hi = __builtin_fabs(bv[r]) < kInf, has_lo = !eqr && __builtin_fabs(rg.lo[r]) < kInf;
+      const double hi = has_hi ? bv[r] : kInf, lo = has_lo ? rg.lo[r] : -kInf;
+      const double beta = __builtin_fmax(has_hi ? __builtin_fabs(hi) : 0.0, has_lo ? __builtin_fabs(lo) : 0.0);
+      const bool pre = ok && has_lo && !has_hi;
+      const double nrm = !(nrm2 <= 0.0) ? nrm2 * rsq1(nrm2) : 0.0;
+      rg.low[r] = pre;
+      rg.w[r] = (ok && has_hi && has_lo) ? hi - lo : kInf;
+      bl[r] = ok ? (pre ? -lo : hi) : 0.0;
+      if (pre) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) E[r][j] = -E[r][j];
+      }
+      thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm + beta) : -kInf;
+      infeasible_row = infeasible_row ||
+                       (ok && nrm2 == 0.0 &&
+                        ((has_hi && hi < -feas_tol * (1.0 + __builtin_fabs(hi))) ||
+                         (has_lo && lo > feas_tol * (1.0 + __builtin_fabs(lo))) ||
+                         (eqr && has_hi && hi > feas_tol * (1.0 + __builtin_fabs(hi))))) ||
+                       (ok && !eqr && rg.w[r] < -feas_tol * (nrm + beta));
+      thr[r] = (eqr && !has_hi) ? __builtin_nan("") : thr[r];
+      act[r] = false;
+      return;
+    }
     bl[r] = ok ? (bv[r] == bv[r] ? bv[r] : kInf) : 0.0;
     thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
     infeasible_row = infeasible_row || (ok && nrm2 == 0.0 && bl[r] < -feas_tol * (1.0 + __builtin_fabs(bl[r])));
@@ -221,6 +280,10 @@ __device__ __forceinline__ void gi_group(
     for (int r = 0; r < MR; ++r) load_a(r, av[r]);
 #pragma unroll
     for (int r = 0; r < MR; ++r) asm volatile("" ::"v"(bv[r]));
+    if constexpr (RG) {
+#pragma unroll
+      for (int r = 0; r < MR; ++r) asm volatile("" ::"v"(rg.lo[r]));
+    }
     asm volatile("" ::"v"(fv));
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -369,6 +432,7 @@ __device__ __forceinline__ void gi_group(
 
   while (!done && it < max_iter) {
     ++it;
+    if constexpr (RG) rg.fresh = false;
     if constexpr (EQ) {
       // the equality phase: one row per trip, whatever its slack (it ends in
       // an ADD or leaves the row out, never in a partial step)
@@ -390,6 +454,17 @@ __device__ __forceinline__ void gi_group(
       uint32_t key = 0u;
 #pragma unroll
       for (int r = 0; r < MR; ++r) {
+        if constexpr (RG) {
+          // the more violated side of the row: the one held (s) or the other
+          // (w - s; NaN or +inf where the row has no other side), same key
+          const double so = rg.w[r] - s[r];
+          const double sv = so < s[r] ? so : s[r];
+          const bool viol = !act[r] && sv < thr[r];
+          const float kf = __builtin_fmaf((float)(-sv), __builtin_amdgcn_rsqf(fn2[r]), 0x1p-100f);
+          const uint32_t kr = (__float_as_uint(kf) & ~31u) | (uint32_t)(l + NL * r);
+          key = viol && kr > key && l + NL * r >= meq ? kr : key;
+          continue;
+        }
         const bool viol = !act[r] && s[r] < thr[r];
         // fn2 in [0, FLT_MAX] (clamped where it shrinks); the 2^-100 floor keeps
         // a violated row's key above 31 -- never 0, the "none violated" key --
@@ -410,6 +485,7 @@ __device__ __forceinline__ void gi_group(
       p = (int)(key & 31u);
       up = 0.0;
       selecting = false;
+      if constexpr (RG) rg.fresh = true;
     }
     clk.tick(4);
     // wave-uniform bound on the active set size (q <= NL always; the clamp
@@ -433,10 +509,31 @@ __device__ __forceinline__ void gi_group(
               for (int j = 0; j < NL; ++j) E[r][j] = -E[r][j];
               s[r] = -s[r];
               neg = 1u;
+              if constexpr (RG) rg.low[r] = !rg.low[r];
             }
         }
         eqs.flip = row_max_u32(neg) != 0u;
       }
+    }
+    if constexpr (RG) {
+      // a row just selected on the side it is not held on changes sides: row p
+      // of D negated in place, s_p = w - s_p; then the QP's lanes learn which
+      // side row p is on (an equality's flip above included)
+      uint32_t lw = 0u;
+      if (l == owner) {
+#pragma unroll
+        for (int r = 0; r < MR; ++r)
+          if (r == prow) {
+            if (rg.fresh && rg.w[r] - s[r] < s[r]) {
+#pragma unroll
+              for (int j = 0; j < NL; ++j) E[r][j] = -E[r][j];
+              s[r] = rg.w[r] - s[r];
+              rg.low[r] = !rg.low[r];
+            }
+            lw = rg.low[r] ? 1u : 0u;
+          }
+      }
+      rg.plow = row_max_u32(lw) != 0u;
     }
     if (l == owner) {
 #pragma unroll
@@ -577,7 +674,8 @@ __device__ __forceinline__ void gi_group(
         invRd = ia;
         iam = p;
         um = up;
-        if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
+        if constexpr (RG) eqs.pneg = rg.plow;
+        else if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
       }
 #pragma unroll
       for (int r = 0; r < MR; ++r) act[r] = act[r] || (l == owner && r == prow);
@@ -600,6 +698,10 @@ __device__ __forceinline__ void gi_group(
       } else if (l == q - 1) {
         um = 0.0;
         iam = -1;
+      }
+      if constexpr (RG) {  // the position's side moves with um and iam
+        const bool pn = __shfl((int)eqs.pneg, (l + 1) & (NL - 1), NL) != 0;
+        eqs.pneg = (l >= k && l < q - 1) ? pn : (l == q - 1 ? false : eqs.pneg);
       }
       // full R (diagonal put back), delete column k: lane l (column l) reads
       // column l + 1 whole, then writes it (in-order DS: every read precedes
@@ -669,10 +771,17 @@ __device__ __forceinline__ void gi_group(
   }
   clk.tick(10);
   // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
-  if constexpr (EQ) um = eqs.pneg ? -um : um;
-  // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
-  if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
-  else um = dual_out(um);
+  // RG: the clamp first, on the multiplier of the side held; then the sign of
+  // a lower-side position, so that H x + f + A^T lam = 0 with the caller's A
+  if constexpr (RG) {
+    um = l >= eqs.q ? dual_out(um) : um;
+    um = eqs.pneg ? -um : um;
+  } else {
+    if constexpr (EQ) um = eqs.pneg ? -um : um;
+    // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
+    if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
+    else um = dual_out(um);
+  }
 
   // ------------------------------------------------------------- outputs
   // (the active rows of A re-read, one coalesced 128-B row per active position)
@@ -746,6 +855,15 @@ __device__ __forceinline__ void gi_group(
     w0 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
   }
   if (live_o && l == 0 && m > 0) at_off<uint32_t>(actg + go0, slo * 4u) = w0;
+  if constexpr (RG) {  // the rows active at their lower bound (never an equality)
+    uint32_t w1 = 0;
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      const unsigned long long bal = __ballot(act[r] && rg.low[r] && l + NL * r >= meq);
+      w1 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
+    }
+    if (lowg && live_o && l == 0 && m > 0) at_off<uint32_t>(lowg + go0, slo * 4u) = w1;
+  }
   // x = -H^{-1} (f + A^T lam): g = f + sum_k u_k a_{iam_k}, then the two solves
   double gl = fl;
   unroll<2>([&](auto H) {
@@ -832,6 +950,21 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_shared_kernel(
                                            feas_tol, 0, nullptr, blockIdx.x, meq, strideH, strideA);
 }
 
+// qpb_solve_range's form: gi_group with RG (on EQ and SH: meq and the strides
+// are arguments, so one set of forms serves plain, equality and shared calls)
+template <int MR, bool N16, bool FULL, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_range_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
+    const double *__restrict__ blg, const double *__restrict__ bug, double *__restrict__ xg,
+    double *__restrict__ lamg, uint32_t *__restrict__ actg, uint32_t *__restrict__ lowg,
+    int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, int meq, long long batch, int max_iter,
+    double feas_tol, long long strideH, long long strideA) {
+  __shared__ double lds[QPB * SLOT];
+  gi_group<MR, N16, FULL, false, true, true, true>(lds, Hg, fg, Ag, bug, xg, lamg, actg, statg, itg, n, m, batch,
+                                                   max_iter, feas_tol, 0, nullptr, blockIdx.x, meq, strideH, strideA,
+                                                   blg, lowg);
+}
+
 }  // namespace qpb
 
 // launcher used by qpb_api.hip
@@ -904,6 +1037,22 @@ extern "C" hipError_t qpb_launch_gi_shared(const qpb_desc *d, int meq, long long
       hipLaunchKernelGGL((qpb::gi_dense_shared_kernel<MR(), N16(), FULL(), false, 3>), dim3((unsigned)blocks),
                          dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, 0,
                          (long long)d->batch, max_iter, tol, strideH, strideA);
+  });
+  return hipGetLastError();
+}
+
+// qpb_solve_range, n <= 16 and 1 <= m <= 32: the six forms with two-sided rows,
+// equality rows 0 .. meq-1 and run-time QP strides of H and A
+extern "C" hipError_t qpb_launch_gi_range(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                          const double *H, const double *f, const double *A, const double *bl,
+                                          const double *bu, double *x, double *lam, uint32_t *active,
+                                          uint32_t *lower, int32_t *status, int32_t *iters, hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_range_kernel<MR(), N16(), FULL(), qpb::kEqOcc>), dim3((unsigned)blocks),
+                       dim3(64), 0, stream, H, f, A, bl, bu, x, lam, active, lower, status, iters, d->n, d->m, meq,
+                       (long long)d->batch, max_iter, tol, strideH, strideA);
   });
   return hipGetLastError();
 }

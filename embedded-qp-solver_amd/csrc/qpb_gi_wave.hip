@@ -96,15 +96,41 @@ static_assert(QPB_MAX_M < (1 << kEqShift));
 // the outputs are the other forms' bit for bit.
 constexpr int kShShift = 28;
 static_assert((QPB_MAX_M << kEqShift) < (1 << kShShift) && (3 << kShShift) > 0);
-template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false>
+// RG (qpb_solve_range, on EQ and SH; see qpb_gi.hip): rows meq .. m-1 are
+// two-sided, bl <= a x <= bu, with bg = bu (may be NULL).  The lane holds one
+// side of its row at a time -- rg.low[0]: the negated, lower-side row of D and
+// slack -- and w = bu - bl gives the other side's slack, w - s; a row selected
+// on the other side is negated in place by its lane, the wave learns row p's
+// side by a ballot, the active position keeps it (pneg moves with um and iam in
+// a DROP), and the multiplier changes sign once at the end.
+// The form's two further pointers are one trailing argument, RangeArgs, that
+// only its instantiation has (the template's parameter pack is empty in every
+// other form, whose signatures and code objects stay as they were).
+struct RangeArgs {
+  const double *bl;  // m per QP, or NULL: no row has a lower bound
+  uint32_t *lower;   // ceil(m/32) words per QP, or NULL: not wanted
+};
+template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false,
+          class... RGA>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
-    double feas_tol, unsigned long long *__restrict__ dbg = nullptr) {
+    double feas_tol, unsigned long long *__restrict__ dbg = nullptr, RGA... rga) {
+  constexpr bool RG = sizeof...(RGA) != 0;
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
   static_assert(!SH || !(STAMP || REDO || BOX), "the shared form is the plain or the EQ kernel's");
+  static_assert(!RG || (EQ && SH && (std::is_same_v<RGA, RangeArgs> && ...) && sizeof...(RGA) == 1),
+                "the range form is built on the EQ and the shared forms and takes one RangeArgs");
   __shared__ double lds[SLOT];
+  [[maybe_unused]] RgState<RG, 1> rg;
+  [[maybe_unused]] const double *blg = nullptr;
+  [[maybe_unused]] uint32_t *lowg = nullptr;
+  if constexpr (RG) {
+    const RangeArgs ra = [](RangeArgs a) { return a; }(rga...);
+    blg = ra.bl;
+    lowg = ra.lower;
+  }
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
     shared = m >> kShShift;
@@ -155,6 +181,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double v = bnd ? bnd[g * n + bi] : (l < n ? kInf : -kInf);
     bv = l < n ? v : -v;
     if (!(bv == bv)) bv = kInf;  // NaN bound: absent
+  } else if constexpr (RG) {
+    // bu and bl, each NULL when no row has that side
+    bv = bg ? bq[rowok ? l : 0] : kInf;
+    rg.lo[0] = blg ? blg[g * (long long)m + (rowok ? l : 0)] : -kInf;
   } else {
     bv = bq[rowok ? l : 0];
   }
@@ -245,11 +275,41 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
 
   clk.tick(0);  // load
   const double nrm2 = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
-  const double bl = rowok ? bv : 0.0;
+  [[maybe_unused]] double rg_b = 0.0, rg_thr = 0.0;
+  [[maybe_unused]] bool rg_inf = false;
+  if constexpr (RG) {
+    // A non-finite bound is an absent side (a NaN, and +-inf of either sign: in
+    // the pair form a row with b = -inf is never violated either).  A row
+    // whose only bound is the lower one is held lower-oriented from here on
+    // (w - s would be inf - inf).  One threshold for both sides, with the
+    // larger finite |bound|; crossed bounds beyond it and a zero row with 0
+    // outside [bl, bu] end the QP as QPB_INFEASIBLE before the loop.  The lower
+    // bound of an equality is not looked at.
+    const bool eqr = rowok && l < meq;
+    const bool has_hi = __builtin_fabs(bv) < kInf, has_lo = !eqr && __builtin_fabs(rg.lo[0]) < kInf;
+    const double hi = has_hi ? bv : kInf, lo = has_lo ? rg.lo[0] : -kInf;
+    const double beta = __builtin_fmax(has_hi ? __builtin_fabs(hi) : 0.0, has_lo ? __builtin_fabs(lo) : 0.0);
+    const bool pre = rowok && has_lo && !has_hi;
+    const double nrm = nrm2 > 0.0 ? nrm2 * rsq(nrm2) : 0.0;
+    rg.low[0] = pre;
+    rg.w[0] = (rowok && has_hi && has_lo) ? hi - lo : kInf;
+    rg_b = rowok ? (pre ? -lo : hi) : 0.0;
+    if (pre) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) E[j] = -E[j];
+    }
+    rg_thr = (rowok && nrm2 > 0.0) ? -feas_tol * (nrm + beta) : -kInf;
+    rg_inf = wave_any((rowok && nrm2 == 0.0 &&
+                       ((has_hi && hi < -feas_tol * (1.0 + __builtin_fabs(hi))) ||
+                        (has_lo && lo > feas_tol * (1.0 + __builtin_fabs(lo))))) ||
+                      (rowok && !eqr && rg.w[0] < -feas_tol * (nrm + beta)));
+  }
+  const double bl = RG ? rg_b : rowok ? bv : 0.0;
   // violated: s / |D row| < -tol (1 + |b| / |D row|), i.e. s < -tol (|D row| + |b|)
-  const double thr = (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
+  const double thr =
+      RG ? rg_thr : (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
   const bool infeasible0 =
-      wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
+      RG ? rg_inf : wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
   // a row of A with a NaN entry or an overflowing norm fails every comparison
   // below and would drop out of the problem unnoticed: QPB_NUMERICAL instead
   // (qpb.h)
@@ -375,6 +435,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   clk.tick(2);  // L store, s, |D row|^2
   while (!done && it < max_iter) {
     ++it;
+    if constexpr (RG) rg.fresh = false;
     if constexpr (EQ) {
       // the equality phase: one row per trip, whatever its slack (it ends in
       // an ADD or leaves the row out, never in a partial step)
@@ -390,16 +451,24 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
 #pragma unroll
           for (int j = 0; j < NP; ++j) E[j] = -E[j];
           s = -s;
+          if constexpr (RG) rg.low[0] = !rg.low[0];
         }
       }
     }
     if (selecting) {
       // dual steepest edge as in qpb_gi.hip: the most violated row by
       // -s / |D[l, q:]| (fp32), the row in the low 6 bits (0 = none violated)
-      const bool viol = !act && s < thr;
+      // RG: the more violated side of the row, the one held (s) or the other
+      // (w - s; NaN or +inf where the row has no other side), under the same key
+      [[maybe_unused]] double sv = s;
+      if constexpr (RG) {
+        const double so = rg.w[0] - s;
+        sv = so < s ? so : s;
+      }
+      const bool viol = !act && (RG ? sv : s) < thr;
       // (fn2 >= 0, clamped where it shrinks; the 2^-100 floor keeps a violated
       // row's key nonzero when the ratio underflows or fn2 overflows)
-      const float kf = __builtin_fmaf((float)(-s), __builtin_amdgcn_rsqf(fn2), 0x1p-100f);
+      const float kf = __builtin_fmaf((float)(-(RG ? sv : s)), __builtin_amdgcn_rsqf(fn2), 0x1p-100f);
       uint32_t kk = viol ? ((__float_as_uint(kf) & ~63u) | (uint32_t)l) : 0u;
       if constexpr (EQ) kk = l >= meq ? kk : 0u;  // the equalities had their turn
       kk = row_max_u32(kk);
@@ -413,6 +482,19 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
       p = (int)(key & 63u);
       up = 0.0;
       selecting = false;
+      if constexpr (RG) rg.fresh = true;
+    }
+    if constexpr (RG) {
+      // a row just selected on the side it is not held on changes sides: row p
+      // of D negated in place, s_p = w - s_p; then the wave learns which side
+      // row p is on (an equality's flip above included)
+      if (rg.fresh && l == p && rg.w[0] - s < s) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j) E[j] = -E[j];
+        s = rg.w[0] - s;
+        rg.low[0] = !rg.low[0];
+      }
+      rg.plow = __ballot(l == p && rg.low[0]) != 0;
     }
     clk.tick(3);  // select
     // row p of D, s_p, |D_p|^2 through LDS; the active columns zeroed there
@@ -557,7 +639,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
         rdg = alpha;
         iam = p;
         um = up;
-        if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
+        if constexpr (RG) eqs.pneg = rg.plow;
+        else if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
       }
       if constexpr (EQ) eqs.q += eqs.sel ? 1 : 0;
       if (li == q) ninvA = -ia;
@@ -578,6 +661,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
       } else if (l == q - 1) {
         um = 0.0;
         iam = -1;
+      }
+      if constexpr (RG) {  // the position's side moves with um and iam
+        const bool pn = __shfl((int)eqs.pneg, (l + 1) & 63) != 0;
+        eqs.pneg = (l >= k && l < q - 1) ? pn : (l == q - 1 ? false : eqs.pneg);
       }
       const int lc = l & (NP - 1);
       wave_lds_sync();
@@ -651,10 +738,17 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double gl = fl;
   const int ll = l & (NP - 1);
   // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
-  if constexpr (EQ) um = eqs.pneg ? -um : um;
-  // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
-  if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
-  else um = dual_out(um);
+  // RG: the clamp first, on the multiplier of the side held; then the sign of
+  // a lower-side position, so that H x + f + A^T lam = 0 with the caller's A
+  if constexpr (RG) {
+    um = l >= eqs.q ? dual_out(um) : um;
+    um = eqs.pneg ? -um : um;
+  } else {
+    if constexpr (EQ) um = eqs.pneg ? -um : um;
+    // lam >= 0 on the inequalities' positions (dual_out: a tie's -eps written as 0)
+    if constexpr (EQ) um = l >= eqs.q ? dual_out(um) : um;
+    else um = dual_out(um);
+  }
   double *lamb = R;  // lambda by row (64 entries over the dead R)
   if constexpr (BOX) {
     // a_k = +e_k (k < n) or -e_{k-n}: g_l = f_l + lam[l] - lam[n + l], the
@@ -748,6 +842,14 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   if (rowok) lamg[g * m + l] = lamb[l];
   if (l < n) xg[g * n + l] = xl;
   const unsigned long long bal = __ballot(act);
+  if constexpr (RG) {  // the rows active at their lower bound (never an equality)
+    const unsigned long long ball = __ballot(act && rg.low[0] && l >= meq);
+    if (l == 0 && m > 0 && lowg) {
+      const int words = (m + 31) / 32;
+      lowg[g * words] = (uint32_t)ball;
+      if (words > 1) lowg[g * words + 1] = (uint32_t)(ball >> 32);
+    }
+  }
   if (l == 0) {
     if (m > 0) {
       const int words = (m + 31) / 32;
@@ -834,5 +936,20 @@ extern "C" hipError_t qpb_launch_gi_wave_shared(const qpb_desc *d, int meq, long
     hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, false, true>), dim3((unsigned)d->batch),
                        dim3(64), 0, stream, H, f, A, b, x, lam, active, status, iters, d->n, mm, (long long)d->batch,
                        max_iter, tol, nullptr);
+  return hipGetLastError();
+}
+
+// qpb_solve_range for the n <= 32, m <= 64 class (d->m >= 1): two-sided rows,
+// equality rows 0 .. meq-1 and the shared launcher's strides
+extern "C" hipError_t qpb_launch_gi_wave_range(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                               const double *H, const double *f, const double *A, const double *bl,
+                                               const double *bu, double *x, double *lam, uint32_t *active,
+                                               uint32_t *lower, int32_t *status, int32_t *iters, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | (strideA == 0 ? QPB_SHARED_A : 0);
+  const int mm = d->m | (meq << qpb::wv::kEqShift) | (shared << qpb::wv::kShShift);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, true, qpb::wv::RangeArgs>),
+                     dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, bu, x, lam, active, status, iters, d->n,
+                     mm, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::RangeArgs{bl, lower});
   return hipGetLastError();
 }

@@ -49,6 +49,15 @@ typedef hipError_t qpb_gi_shared_launcher(const qpb_desc *d, int meq, long long 
                                           hipStream_t stream);
 QPB_LAUNCHER qpb_gi_shared_launcher qpb_launch_gi_shared,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_wave_shared;                             // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_range: two-sided rows bl <= A x <= bu (either of bl, bu may be NULL:
+// no row has that side), equality rows 0 .. meq-1 (meq >= 0) and the shared
+// launchers' strides; d->m >= 1, d->flags == 0; lower may be NULL
+typedef hipError_t qpb_gi_range_launcher(const qpb_desc *d, int meq, long long strideH, long long strideA,
+                                         const double *H, const double *f, const double *A, const double *bl,
+                                         const double *bu, double *x, double *lam, uint32_t *active, uint32_t *lower,
+                                         int32_t *status, int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_range_launcher qpb_launch_gi_range,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_range;                            // n <= 32, m <= 64 (qpb_gi_wave.hip)
 // qpb_solve_shared_backward, pass 1: qpb_launch_kkt_bwd with the same strides
 // (gH / gA NULL where pass 2 sums the gradient)
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long strideH, long long strideA,

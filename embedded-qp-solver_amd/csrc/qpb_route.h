@@ -152,6 +152,29 @@ static_assert(route_shared(kSharedMaxN, kSharedMaxM).step > 0 && route_shared(kS
 static_assert(route_shared_bwd(kSharedMaxN, kSharedMaxM).step > 0 && route_shared_bwd(kSharedMaxN + 1, 1).step == 0 &&
               route_shared_bwd(1, kSharedMaxM + 1).step == 0);
 
+// qpb_solve_range with m > 0: the RG forms of the two wavefront-level classes,
+// whatever meq and the shared bits (the forms take both at run time); above
+// them -- the Gram class -- there is no range form yet: step 0, and the call is
+// unsupported.
+constexpr Route route_range(int n, int m) {
+  if (n <= 16 && m <= 32) return {Kernel::gi_dense, step_of(Kernel::gi_dense)};
+  if (n <= 32 && m <= 64) return {Kernel::gi_wave, step_of(Kernel::gi_wave)};
+  return {Kernel::gi_gram, 0};
+}
+constexpr int kRangeMaxN = 32, kRangeMaxM = 64;  // the limit route_range's step 0 stands for
+
+static_assert(route_range(16, 32).kernel == Kernel::gi_dense && route_range(1, 1).kernel == Kernel::gi_dense);
+static_assert(route_range(16, 33).kernel == Kernel::gi_wave && route_range(17, 1).kernel == Kernel::gi_wave);
+static_assert(route_range(32, 64).kernel == Kernel::gi_wave && route_range(32, 64).step == 1LL << 25);
+static_assert(route_range(16, 32).step == 1LL << 27);
+static_assert(route_range(33, 1).step == 0 && route_range(32, 65).step == 0 && route_range(1, 65).step == 0 &&
+              route_range(128, 256).step == 0);
+static_assert(route_range(kRangeMaxN, kRangeMaxM).step > 0 && route_range(kRangeMaxN + 1, 1).step == 0 &&
+              route_range(1, kRangeMaxM + 1).step == 0);
+// a range solve's outputs go to qpb_solve_backward unchanged: the same classes
+static_assert(route_range(16, 32).kernel == route_bwd(16, 32).kernel &&
+              route_range(32, 64).kernel == route_bwd(32, 64).kernel);
+
 // The slice plan of the batch sum (qpb_kkt_bwd_sum.hip): `slots` consecutive
 // slices of `per` QPs, the last one shorter; one wavefront and one workspace
 // slot per slice.  A function of the batch size alone -- not of the device --

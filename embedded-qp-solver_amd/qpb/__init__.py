@@ -16,6 +16,7 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve_shared(H, f, A, b, meq) -> qpb_solve_shared (a 2-D H and / or A: one matrix for the whole batch)
     solve_shared_backward(H, A, sol, gx) -> qpb_solve_shared_backward (a shared operand's gradient summed over the batch)
     solve_box_backward(H, sol, gx) -> qpb_solve_box_backward (gradients of a box solve, n <= 32)
+    solve_range(H, f, A, bl, bu, meq) -> qpb_solve_range (two-sided rows bl <= A x <= bu, signed lam; n <= 32, m <= 64)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
     ref_generate(n, B, seed)   -> qpb_ref_generate (the reference generator, bit for bit)
@@ -87,6 +88,10 @@ _lib.qpb_solve_shared_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32]
 _lib.qpb_solve_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_shared_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_range.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 12
+_lib.qpb_solve_range.restype = ctypes.c_int
+_lib.qpb_solve_range_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 11
+_lib.qpb_solve_range_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
 _lib.qpb_solve_box_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
@@ -427,6 +432,85 @@ def solve_shared_host(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, 
                                     p(b) if m else None, p(x), p(lam), p(act), p(st), p(it))
     _check(rc, "qpb_solve_shared_host")
     return Solution(x, lam, act, st, it)
+
+
+class RangeSolution(NamedTuple):
+    x: object       # (B, n) float64
+    lam: object     # (B, m) float64, signed: >= 0 at the upper bound, <= 0 at the lower one
+    active: object  # (B, ceil(m/32)) int32 (uint32 bit pattern): active on either side
+    lower: object   # (B, ceil(m/32)) int32 (uint32 bit pattern): active at the lower bound
+    status: object  # (B,) int32
+    iters: object   # (B,) int32
+
+
+def _empty_range_solution(B: int, n: int, m: int, dev) -> RangeSolution:
+    import torch
+    s = _empty_solution(B, n, m, dev)
+    return RangeSolution(s.x, s.lam, s.active, torch.empty((B, (m + 31) // 32), dtype=torch.int32, device=dev),
+                         s.status, s.iters)
+
+
+def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                out: RangeSolution | None = None, stream=None) -> RangeSolution:
+    """Batched min 1/2 x^T H x + f^T x s.t. A[:meq] x = bu[:meq], bl[meq:] <= A[meq:] x <= bu[meq:]
+    on the GPU (qpb_solve_range; torch CUDA float64 tensors as for ``solve``).
+
+    The constraint form of OSQP and qpOASES: ``l``, ``u`` are ``bl``, ``bu`` and
+    ``y`` is ``lam`` with the same sign (H x + f + A^T lam = 0).  ``bl`` or
+    ``bu`` may be None (no row has that side); NaN and +-inf entries are absent
+    bounds.  A 2-D ``H`` (n, n) and / or ``A`` (m, n) is one matrix for the whole
+    batch, as in ``solve_shared``.  ``sol.active`` with ``sol.lam`` is what
+    ``solve_backward`` reads; ``sol.lower`` marks the rows active at ``bl``.
+    n <= 32 and m <= 64."""
+    import torch
+    if bl is None and bu is None and A is not None:
+        raise ValueError("qpb.solve_range needs at least one of bl and bu")
+    some = bu if bu is not None else bl
+    B, n, m, shared = _shared_shape("qpb.solve_range", H, f, A, some)
+    for t in (bl, bu):
+        if m and t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != f.device
+                                    or tuple(t.shape) != (B, m)):
+            raise ValueError("bl and bu must be contiguous float64 (B, m) tensors on the inputs' device")
+    if out is None:
+        out = _empty_range_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_range(ctypes.byref(d), int(meq), shared, _ptr(H), _ptr(f), _ptr(A) if m else None,
+                              _ptr(bl) if m else None, _ptr(bu) if m else None, _ptr(out.x), _ptr(out.lam),
+                              _ptr(out.active), _ptr(out.lower), _ptr(out.status), _ptr(out.iters),
+                              _stream_ptr(stream))
+    _check(rc, "qpb_solve_range")
+    return out
+
+
+def solve_range_host(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0) -> RangeSolution:
+    """numpy in / numpy out (qpb_solve_range_host): ``solve_range`` with host arrays."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    B, n = f.shape
+    m = 0 if A is None else A.shape[-2]
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        bl = None if bl is None else np.ascontiguousarray(bl, dtype=np.float64)
+        bu = None if bu is None else np.ascontiguousarray(bu, dtype=np.float64)
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if m and A.ndim == 2 else 0)
+    if H.shape not in ((n, n), (B, n, n)) or (m and (A.shape not in ((m, n), (B, m, n))
+                                                     or any(t is not None and t.shape != (B, m) for t in (bl, bu)))):
+        raise ValueError("shape mismatch")
+    w = (m + 31) // 32
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, w), dtype=np.uint32)
+    low = np.zeros((B, w), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_range_host(ctypes.byref(d), int(meq), shared, p(H), p(f), p(A) if m else None,
+                                   p(bl) if m else None, p(bu) if m else None, p(x), p(lam), p(act), p(low), p(st),
+                                   p(it))
+    _check(rc, "qpb_solve_range_host")
+    return RangeSolution(x, lam, act, low, st, it)
 
 
 def solve_shared_backward(H, A, sol: Solution, gx, *, need=NEED_ALL, stream=None):

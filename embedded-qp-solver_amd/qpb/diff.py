@@ -16,6 +16,11 @@ is (n, n), and no (B, n, n) or (B, m, n) tensor is ever allocated.
 
 ``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
 and ub (``qpb.solve_box_backward``, n <= 32).
+
+``solve_range(H, f, A, bl, bu, meq)`` is ``qpb.solve_range`` with gradients for
+H, f, A, bl and bu: the backward is ``qpb.solve_backward`` (or the shared one)
+on the range solve's outputs, its ``gb`` routed to ``bl`` or ``bu`` by the
+``lower`` bits.
 """
 from __future__ import annotations
 
@@ -81,6 +86,60 @@ class BoxQPFunction(torch.autograd.Function):
         # on torch's current stream; above n = 32 this raises QPBError(ERR_UNSUPPORTED)
         gH, gf, glb, gub = qpb.solve_box_backward(H, sol, gx.contiguous(), need=wanted)
         return gH, gf, glb, gub, None, None
+
+
+class RangeQPFunction(torch.autograd.Function):
+    """x*(H, f, A, bl, bu) of min 1/2 x'Hx + f'x s.t. A[:meq] x = bu[:meq], bl[meq:] <= A[meq:] x <= bu[meq:]."""
+
+    @staticmethod
+    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol):
+        H, f, A = H.contiguous(), f.contiguous(), A.contiguous()
+        bl = None if bl is None else bl.contiguous()
+        bu = None if bu is None else bu.contiguous()
+        # above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
+        sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.shared = H.dim() == 2 or A.dim() == 2
+        ctx.meq = meq
+        ctx.has = (True, True, True, bl is not None, bu is not None)
+        ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.lower, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        H, A, x, lam, active, lower, status = ctx.saved_tensors
+        want = [w and has for w, has in zip(ctx.needs_input_grad[:5], ctx.has)]
+        wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if want[3] or want[4] else [])
+        if not wanted:
+            return (None,) * 8
+        sol = qpb.Solution(x, lam, active, status, None)
+        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
+        gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
+        gbl = gbu = None
+        if gb is not None:
+            # every element of gb goes to the bound its row is active at: bl where the
+            # `lower` bit is set (never on an equality), bu everywhere else
+            m = gb.shape[1]
+            rows = torch.arange(m, device=gb.device)
+            low = ((lower[:, rows // 32] >> (rows % 32)) & 1).bool()
+            zero = torch.zeros_like(gb)
+            if want[3]:
+                gbl = torch.where(low, gb, zero)
+            if want[4]:
+                gbu = torch.where(low, zero, gb)
+        return gH, gf, gA, gbl, gbu, None, None, None
+
+
+def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+    """Differentiable batched solve with two-sided rows (``qpb.solve_range`` with
+    gradients): returns ``(x, status)``; ``x`` carries gradients to whichever of
+    H, f, A, bl and bu require them.  The backward is ``qpb.solve_backward`` (with
+    a 2-D H or A, ``qpb.solve_shared_backward``) on the solve's x, signed lam,
+    active and status; its ``gb`` goes to ``bu`` on the rows < meq and on the
+    rows active at their upper bound, to ``bl`` on the rows whose ``lower`` bit
+    is set.  A bound passed as None gets no gradient.  n <= 32 and m <= 64: above
+    that the forward raises ``QPBError(ERR_UNSUPPORTED)``."""
+    return RangeQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol))
 
 
 def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0):

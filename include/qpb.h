@@ -15,6 +15,7 @@
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
+ *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -386,6 +387,85 @@ int qpb_solve_shared_backward_host(const qpb_desc *desc, int32_t shared,
 				   const int32_t *status, const double *gx,
 				   double *gH, double *gf, double *gA,
 				   double *gb);
+
+/* Two-sided rows, the form OSQP and qpOASES state their constraints in:
+ *   min 1/2 x^T H x + f^T x   s.t.   a_i x = bu_i            (rows i < meq; bl_i is not read)
+ *                                    bl_i <= a_i x <= bu_i   (rows meq <= i < m)
+ * Layouts are qpb_solve_eq's, with bl and bu each m per QP; `shared` is
+ * qpb_solve_shared's bit set for H and A (bl and bu are always per QP).  A row
+ * is taken natively -- one row of A L^-T and an orientation bit, in the RG forms
+ * of qpb_gi.hip and qpb_gi_wave.hip -- where the pair a x <= bu, -a x <= -bl
+ * would double m.  That pair rewrite through qpb_solve_eq is the specification
+ * wherever this text is silent.
+ * Outputs
+ *   x, status, iters   as qpb_solve_eq.
+ *   lam (m per QP)     signed, in OSQP's convention: H x + f + A^T lam = 0 with
+ *                      the caller's A.  lam_i >= 0 exactly on a row active at
+ *                      its upper bound, lam_i <= 0 exactly on a row active at
+ *                      its lower bound (a tie's -eps of the side held is
+ *                      written as 0 before the sign), free on an equality,
+ *                      0 outside `active`.
+ *   active             ceil(m/32) words per QP: bit i is set when row i is in
+ *                      the final active set, on either side -- exactly the
+ *                      array qpb_solve_backward and qpb_solve_shared_backward
+ *                      read, with this lam.
+ *   lower              ceil(m/32) words per QP, may be NULL: bit i is set when
+ *                      row i is active at its LOWER bound.  lower is a subset
+ *                      of active bit for bit; bits of rows < meq are always
+ *                      clear.  It settles the side of a weakly active row
+ *                      (lam_i = 0), which the sign of lam cannot.
+ * Every element of every non-NULL output of every QP is written, whatever the
+ * status, and a QP's outputs depend on its own inputs only.
+ * Semantics
+ *   absent bounds      a bu_i that is NaN or +inf is no upper bound, a bl_i that
+ *                      is NaN or -inf no lower bound; with both absent the row
+ *                      is absent.  bu_i = -inf or bl_i = +inf on a row >= meq
+ *                      is an absent side as well: that is what the pair rewrite
+ *                      makes of it (a row with b = -inf is never violated).  A
+ *                      non-finite bu_i on a row < meq is QPB_NUMERICAL, as in
+ *                      qpb_solve_eq.  bl or bu may be NULL: every row lacks
+ *                      that side.
+ *   tolerance          a row is violated on a side when the violation exceeds
+ *                      feas_tol (|a_i| + beta_i), beta_i the larger of the
+ *                      finite |bl_i| and |bu_i|: one threshold per row.
+ *   crossed bounds     bl_i - bu_i above that threshold: QPB_INFEASIBLE from
+ *                      the set-up (iters = 0, lam = 0, active = 0, lower = 0).
+ *                      A negative width inside the threshold is a zero width.
+ *   zero row of A      infeasible iff 0 lies outside [bl_i, bu_i] by more than
+ *                      feas_tol (1 + |bound|): qpb_solve's rule, both signs.
+ *   zero width         bl_i == bu_i on a row >= meq is legal: the row is taken
+ *                      on whichever side is violated and may be dropped and
+ *                      taken again, with the x of the meq form.  Sorting such
+ *                      rows first and passing meq is the faster way to say it.
+ *   QPB_MAX_ITER, QPB_INFEASIBLE found by the iteration: the contract's
+ *                      sentences hold with the signed lam,
+ *                      x = -H^-1 (f + A^T lam).
+ *   default max_iter   4 (n + m) + 8.
+ *   m == 0             the call is qpb_solve; `lower` has no words and is not
+ *                      written.
+ * Errors, in order: the descriptor as qpb_solve; meq < 0, desc->flags != 0, a bit
+ * of `shared` outside QPB_SHARED_H | QPB_SHARED_A, each QPB_ERR_INVALID_ARG;
+ * n > 32 or m > 64 QPB_ERR_UNSUPPORTED; meq > m QPB_ERR_INVALID_ARG; batch == 0
+ * returns 0 before the pointers are looked at; missing pointers
+ * QPB_ERR_INVALID_ARG (H, f, x and status always; with m > 0 A, lam, active and
+ * at least one of bl and bu); a missing device last.
+ * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
+ * with m <= 64.  Follow-ups: the n <= 128 Gram class, QPB_FLAG_MIXED,
+ * qpb_solve_sections and a range form of qpb_solve_box (general rows beside a
+ * box) have no range form.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_range(const qpb_desc *desc, int32_t meq, int32_t shared,
+		    const double *H, const double *f, const double *A,
+		    const double *bl, const double *bu, double *x, double *lam,
+		    uint32_t *active, uint32_t *lower, int32_t *status,
+		    int32_t *iters, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (a shared operand is one matrix). */
+int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
+			 const double *H, const double *f, const double *A,
+			 const double *bl, const double *bu, double *x,
+			 double *lam, uint32_t *active, uint32_t *lower,
+			 int32_t *status, int32_t *iters);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved

@@ -10,7 +10,9 @@ directives (registers, LDS, scratch), must be the same in NEW.  Labels and
 comments are dropped, so the kernels may move inside a file.  A kernel template
 that gained a trailing template parameter whose default is `false` (and a
 kernel that became such a template) is the same kernel under a longer name:
-it is found through its demangled name (c++filt, or $CXXFILT).  Kernels that
+it is found through its demangled name (c++filt, or $CXXFILT).  So is a kernel
+template that gained a trailing template parameter pack, empty in the old
+instantiations: another symbol with the same demangled name.  Kernels that
 only NEW has are counted.  Exit status 1 when a kernel of OLD changed or is gone.
 """
 import os
@@ -39,6 +41,11 @@ def successor(name, old_dem, new_dem):
     grown = (head[:-1] + ", false>" if head.endswith(">") else head + "<false>") + paren + args
     for n, dn in new_dem.items():
         if dn == grown:
+            return n
+    # a template that gained a trailing parameter pack, empty here: another
+    # symbol, the same demangled name
+    for n, dn in new_dem.items():
+        if dn == d:
             return n
     return None
 
