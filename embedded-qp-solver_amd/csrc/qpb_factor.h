@@ -1,0 +1,76 @@
+// qpb_factor.h -- the layout of a factor buffer (qpb_factor_shared ->
+// qpb_solve_factored): what one shared H and A turn into once, so that a solve
+// starts from L and D = A L^-T instead of computing them per QP.  Plain C++
+// without a HIP header: the host compiler builds it alone, the factor kernels
+// (which write a buffer) and the factored solve forms (which read it) share it.
+//
+// A buffer is self-contained -- the solve takes neither H nor A -- and belongs
+// to one (n, m): the kernel class, and with it the layout, follows from the
+// shape exactly as the route does.  All offsets are in doubles.
+//
+//   header (kHdr)   [0] what the set-up found that does not depend on b: 0,
+//                   QPB_NOT_SPD or QPB_NUMERICAL (a row of A with a NaN entry or
+//                   a non-finite squared norm), as a double; [1] n; [2] m;
+//                   [3] 16 or 32, the padded n of the class
+//   L               the Cholesky factor of H, padded as the class's kernel pads it
+//   D               A L^-T, one row per lane as the class's kernel holds it
+//   an2, an, dn2    per row |a_r|^2, |a_r| = |a_r|^2 rsqrt(|a_r|^2) (the value the
+//                   unfactored kernel forms its threshold from) and |D_r|^2
+//   A               the caller's A, row-major m x n (the x recovery re-reads the
+//                   active rows)
+//
+// L and D are stored for the solve kernels' loads: a load instruction's lanes
+// read consecutive addresses.
+//   n <= 16, m <= 32 (gi_dense: lane l of a QP's 16 holds row l of L and rows
+//   l + 16 r of D, r < MR):
+//     L   [t][l][c], t < 8, c < 2: L[l][2t + c] -- one 16-byte load per lane and
+//         t, the 16 lanes read 256 contiguous bytes; 16 x 16, the identity
+//         outside n
+//     D   [r][t][l][c]: D[l + 16 r][2t + c], rows >= m and columns >= n zero
+//     an2, an, dn2   [r][l]
+//   otherwise, n <= 32, m <= 64 (gi_wave: lane l of 64 holds row l of D):
+//     L   packed rows, L[i][j] at i (i + 1) / 2 + j, 32 rows (zero from row n
+//         on): copied flat into the kernel's LDS, element i 64 + l by lane l
+//     D   [t][l][c], t < 16, c < 2: D[l][2t + c] -- the 64 lanes read 1 KiB
+//     an2, an, dn2   [l]
+#pragma once
+
+namespace qpb {
+namespace fct {
+
+constexpr int kHdr = 8;
+constexpr int kMaxN = 32, kMaxM = 64;  // the limit of qpb_factor_shared and qpb_solve_factored
+
+struct Layout {
+  bool dense;     // the n <= 16, m <= 32 class
+  int mr;         // dense: rows of D per lane
+  long long L;    // offsets
+  long long D, an2, an, dn2, A;
+  long long size;  // doubles in all
+};
+
+constexpr Layout layout(int n, int m) {
+  Layout y{};
+  y.dense = n <= 16 && m <= 32;
+  y.mr = m <= 16 ? 1 : 2;
+  const long long lsize = y.dense ? 256 : 32 * 33 / 2;
+  const long long rows = y.dense ? 16LL * y.mr : 64, cols = y.dense ? 16 : 32;
+  y.L = kHdr;
+  y.D = y.L + lsize;
+  y.an2 = y.D + rows * cols;
+  y.an = y.an2 + rows;
+  y.dn2 = y.an + rows;
+  y.A = y.dn2 + rows;
+  y.size = y.A + (long long)m * n;
+  return y;
+}
+
+static_assert(layout(16, 32).dense && layout(16, 32).mr == 2 && !layout(16, 33).dense && !layout(17, 0).dense);
+static_assert(layout(16, 32).size == 8 + 256 + 512 + 96 + 512 && layout(1, 0).size == 8 + 256 + 256 + 48);
+static_assert(layout(32, 64).size == 8 + 528 + 2048 + 192 + 2048);
+// every section starts on a 16-byte boundary (the b128 loads of L and D)
+static_assert(layout(16, 32).D % 2 == 0 && layout(16, 32).L % 2 == 0 && layout(32, 64).D % 2 == 0 &&
+              layout(7, 5).D % 2 == 0 && layout(20, 3).D % 2 == 0);
+
+}  // namespace fct
+}  // namespace qpb

@@ -51,6 +51,7 @@
 // no LDS round trip, no copy of the vector in every lane.
 // No branch or select compares the lane id with a compile-time constant:
 // such masks are hoisted by the compiler and end up spilled (SGPR pressure).
+#include "qpb_factor.h"  // the factor buffer of qpb_factor_shared / qpb_solve_factored
 #include "qpb_launch.h"  // with qpb.h
 #include "qpb_row16.h"   // the QP's LDS slot and the steps shared with gi_box and kkt_bwd
 
@@ -104,7 +105,19 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 // active at their lower bound.  The norms (thr, ddr, fn2) do not depend on
 // the side.  A dropped row keeps its side; its slack follows the updates like
 // any inactive row's, and it can come back on either side.
-template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false>
+// FM (qpb_factor_shared and qpb_solve_factored; qpb_factor.h has the buffer):
+//   1  the factor kernel's body: ONE problem (batch 1, no f and no b), this
+//      form's own load and sweep, then L, D, the rows' norms, A and what the
+//      set-up found go to the buffer `xg` (and the finding to statg, if given),
+//      and nothing else runs
+//   2  the factored solve, on SH with both strides 0: Hg is the buffer and Ag
+//      its copy of A.  No H or A is loaded and nothing is staged: the lane's row
+//      of L and its MR rows of D come from the buffer, thr from the stored |a_r|,
+//      ddr and fn2 from the stored |D_r|^2; then y = L^-1 f by a lane-parallel
+//      forward substitution and s = b + D y, n (1 + MR) DPP-fused FMAs in place
+//      of the sweep.  From there on -- the loop and the outputs -- the code is
+//      the other forms', plain and EQ.
+template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false, int FM = 0>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
@@ -116,6 +129,7 @@ __device__ __forceinline__ void gi_group(
   static_assert(!FULL || N16, "FULL implies n == 16");
   static_assert(!RG || (EQ && SH), "the range form is built on the EQ and the shared forms");
   static_assert(!SH || !STAMP, "the shared form has no stamped build");
+  static_assert(FM == 0 || (!STAMP && !RG && (FM == 1 ? !EQ && !SH : SH)), "the factor forms are plain, EQ or SH ones");
   SectionClock<STAMP> clk;
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -167,7 +181,12 @@ __device__ __forceinline__ void gi_group(
   // b and f with the matrices (same round trip)
   double bv[MR];
   [[maybe_unused]] RgState<RG, MR> rg;
-  if constexpr (RG) {
+  // FM: per row |a_r|^2 and |a_r| (1: found by row_norms; 2: from the buffer)
+  [[maybe_unused]] double an2[MR], an1[MR];
+  if constexpr (FM == 1) {
+#pragma unroll
+    for (int r = 0; r < MR; ++r) bv[r] = 0.0;
+  } else if constexpr (RG) {
     // bu and bl, each NULL (wave-uniform) when no row has that side
     const double *lo_s = blg ? blg + gi0 * (long long)m : nullptr;
 #pragma unroll
@@ -181,7 +200,8 @@ __device__ __forceinline__ void gi_group(
     for (int r = 0; r < MR; ++r)
       bv[r] = at_off<double>(bs, (sl * (uint32_t)m + (uint32_t)((FULL || l + NL * r < m) ? l + NL * r : 0)) * 8u);
   }
-  const double fv = at_off<double>(fg + gi0 * n, (sl * un + (uint32_t)(l < n ? l : n - 1)) * 8u);
+  double fv = 0.0;
+  if constexpr (FM != 1) fv = at_off<double>(fg + gi0 * n, (sl * un + (uint32_t)(l < n ? l : n - 1)) * 8u);
   const double fl = (N16 || l < n) ? fv : 0.0;
   [[maybe_unused]] const int hr = l >> 3, hc = 2 * (l & 7);
   // stage 16 rows of a 16-column matrix (as loaded) in this QP's slot (L and
@@ -204,7 +224,13 @@ __device__ __forceinline__ void gi_group(
   // gi_wave and gi_gram, cost 168 VGPRs instead of 162 at MR = 2 and 12 bytes
   // of scratch in the n = 16, m < 32 form
   auto row_norms = [&](int r, const double (&row)[NL]) {
-    const double nrm2 = dot2<NL>([&](int j) { return row[j]; }, [&](int j) { return row[j]; });
+    double nrm2;
+    if constexpr (FM == 2) nrm2 = an2[r];
+    else nrm2 = dot2<NL>([&](int j) { return row[j]; }, [&](int j) { return row[j]; });
+    if constexpr (FM == 1) {
+      an2[r] = nrm2;
+      an1[r] = !(nrm2 <= 0.0) ? nrm2 * rsq1(nrm2) : 0.0;
+    }
     const bool ok = FULL || l + NL * r < m;
     if constexpr (RG) {
       // A non-finite bound is an absent side (a NaN, and +-inf of either sign:
@@ -239,7 +265,8 @@ __device__ __forceinline__ void gi_group(
       return;
     }
     bl[r] = ok ? (bv[r] == bv[r] ? bv[r] : kInf) : 0.0;
-    thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
+    if constexpr (FM == 2) thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (an1[r] + __builtin_fabs(bl[r])) : -kInf;
+    else thr[r] = !(nrm2 <= 0.0) ? -feas_tol * (nrm2 * rsq1(nrm2) + __builtin_fabs(bl[r])) : -kInf;
     infeasible_row = infeasible_row || (ok && nrm2 == 0.0 && bl[r] < -feas_tol * (1.0 + __builtin_fabs(bl[r])));
     if constexpr (EQ) {
       // an equality: a zero row is infeasible for b of either sign, and a
@@ -251,7 +278,39 @@ __device__ __forceinline__ void gi_group(
     }
     act[r] = false;
   };
-  if constexpr (N16) {
+  [[maybe_unused]] double fdn[MR];    // FM == 2: |D[r,:]|^2 from the buffer
+  [[maybe_unused]] bool fspd = true;  // FM == 2: the buffer's H was positive definite
+  if constexpr (FM == 2) {
+    // The buffer in place of H and A: every load is 16 bytes per lane at
+    // consecutive addresses over the QP's lanes, the same for the wave's four
+    // QPs (and every other wave: the few KiB stay in the caches).  The offsets
+    // depend on MR alone (qpb_factor.h).
+    constexpr uint32_t oL = fct::kHdr, oD = oL + NL * NL, oN = oD + MR * NL * NL;
+    static_assert(fct::layout(NL, NL * MR).L == oL && fct::layout(NL, NL * MR).D == oD &&
+                  fct::layout(NL, NL * MR).an2 == oN && fct::layout(1, NL * MR).dn2 == oN + 2 * MR * NL);
+    fspd = Hs[0] != (double)QPB_NOT_SPD;
+    const uint32_t lo = (uint32_t)l * 16u;
+#pragma unroll
+    for (int t = 0; t < NL / 2; ++t) {
+      const double2 v = at_off<double2>(Hs, (oL + (uint32_t)t * 2u * NL) * 8u + lo);
+      Lr[2 * t] = v.x;
+      Lr[2 * t + 1] = v.y;
+    }
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+#pragma unroll
+      for (int t = 0; t < NL / 2; ++t) {
+        const double2 v = at_off<double2>(Hs, (oD + (uint32_t)(r * (NL / 2) + t) * 2u * NL) * 8u + lo);
+        E[r][2 * t] = v.x;
+        E[r][2 * t + 1] = v.y;
+      }
+      an2[r] = at_off<double>(Hs, (oN + (uint32_t)(r * NL)) * 8u + (uint32_t)l * 8u);
+      an1[r] = at_off<double>(Hs, (oN + (uint32_t)((MR + r) * NL)) * 8u + (uint32_t)l * 8u);
+      fdn[r] = at_off<double>(Hs, (oN + (uint32_t)((2 * MR + r) * NL)) * 8u + (uint32_t)l * 8u);
+    }
+#pragma unroll
+    for (int r = 0; r < MR; ++r) row_norms(r, E[r]);
+  } else if constexpr (N16) {
     // Coalesced 16-byte loads: one instruction reads 2 whole rows (256 B) of
     // each of the wave's 4 QPs -- lane l gets row 2t + (l>>3), columns
     // 2(l&7), 2(l&7)+1.  Rows reach their owner lane through a transpose in
@@ -335,7 +394,31 @@ __device__ __forceinline__ void gi_group(
 
   bool spd = true;
   double ya = fl;
-  {
+  if constexpr (FM == 2) {
+    // ---- y = L^{-1} f and s = b + D y from the stored L and D.  Lane-parallel
+    // forward substitution on the negated accumulator na = -(f - sum L y): step k
+    // forms t = na ninv, which is y_k on lane k (ninv = -1 / L[l][l]), and every
+    // FMA of the step reads it from lane k by its own DPP broadcast -- the MR
+    // rows' s += D[r][k] y_k and the lane's na += L[l][k] y_k.  t is a VALU
+    // result read through DPP: dpp_ready issues the wait states.  Lane k's own na
+    // becomes 0 at step k and is dead from there on, like the entries of its row
+    // of L right of the diagonal (zero in the buffer).
+    spd = fspd;
+    store_l(Lp, l, Lr);  // kept for the final solves
+    const double ninv = -rcp1(Lp[lrow(l) + l]);
+    wave_lds_sync();
+    double na = -ya;
+#pragma unroll
+    for (int r = 0; r < MR; ++r) s[r] = bl[r];
+    unroll<NL>([&](auto K) {
+      constexpr int k = K;
+      const double t = na * ninv;
+      dpp_ready(t);
+#pragma unroll
+      for (int r = 0; r < MR; ++r) fmac_bc<k>(s[r], t, E[r][k]);
+      fmac_bc<k>(na, t, Lr[k]);
+    });
+  } else {
     // ---- H = L L^T, D = A L^{-T}, y = L^{-1} f: one right-looking sweep.
     // Step k: pr = row k of the current Schur complement (lane k's Lr, DPP
     // broadcast) = column k by symmetry, so L[j][k] = pr[j] / sqrt(akk) and
@@ -392,9 +475,44 @@ __device__ __forceinline__ void gi_group(
   // every row and end the QP INFEASIBLE.
 #pragma unroll
   for (int r = 0; r < MR; ++r) {
-    ddr[r] = __builtin_fminf((float)dot2<NL>([&](int j) { return E[r][j]; }, [&](int j) { return E[r][j]; }),
-                             3.402823466e38f);
+    if constexpr (FM == 2)
+      ddr[r] = (float)fdn[r];
+    else
+      ddr[r] = __builtin_fminf((float)dot2<NL>([&](int j) { return E[r][j]; }, [&](int j) { return E[r][j]; }),
+                               3.402823466e38f);
     fn2[r] = ddr[r];
+  }
+  if constexpr (FM == 1) {
+    // ---- the factor kernel ends here: the live row (QP 0) writes the buffer
+    bool nan_row = false;
+#pragma unroll
+    for (int r = 0; r < MR; ++r) nan_row = nan_row || ((FULL || l + NL * r < m) && !(an2[r] < kInf));
+    const bool anynan = row_min(nan_row ? -1.0 : 0.0) < 0.0;
+    const int found = !spd ? QPB_NOT_SPD : anynan ? QPB_NUMERICAL : QPB_OK;
+    if (live) {
+      constexpr int oL = fct::kHdr, oD = oL + NL * NL, oN = oD + MR * NL * NL, oA = oN + 3 * MR * NL;
+      static_assert(fct::layout(NL, NL * MR).D == oD && fct::layout(NL, NL * MR).an2 == oN &&
+                    fct::layout(1, NL * MR).A == oA && fct::layout(NL, NL * MR).size == oA + NL * NL * MR);
+      double *fac = xg;
+      if (l < fct::kHdr) fac[l] = l == 0 ? (double)found : l == 1 ? (double)n : l == 2 ? (double)m : l == 3 ? 16.0 : 0.0;
+      if (l == 0 && statg) statg[0] = found;
+#pragma unroll
+      for (int t = 0; t < NL / 2; ++t)  // zero right of the diagonal (the sweep leaves dead values there)
+        *reinterpret_cast<double2 *>(&fac[oL + (t * NL + l) * 2]) =
+            make_double2(2 * t <= l ? Lr[2 * t] : 0.0, 2 * t + 1 <= l ? Lr[2 * t + 1] : 0.0);
+#pragma unroll
+      for (int r = 0; r < MR; ++r) {
+#pragma unroll
+        for (int t = 0; t < NL / 2; ++t)
+          *reinterpret_cast<double2 *>(&fac[oD + ((r * (NL / 2) + t) * NL + l) * 2]) =
+              make_double2(E[r][2 * t], E[r][2 * t + 1]);
+        fac[oN + r * NL + l] = an2[r];
+        fac[oN + (MR + r) * NL + l] = an1[r];
+        fac[oN + (2 * MR + r) * NL + l] = (double)ddr[r];
+      }
+      for (int i = l; i < m * n; i += NL) fac[oA + i] = As[i];
+    }
+    return;
   }
   clk.tick(1);
 
@@ -965,6 +1083,30 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_range_kernel(
                                                    blg, lowg);
 }
 
+// qpb_factor_shared's kernel: one workgroup, whose first row factors the one
+// problem with this form's own load and sweep (gi_group with FM = 1)
+template <int MR, bool N16, bool FULL>
+__global__ __launch_bounds__(64) void gi_dense_factor_kernel(const double *__restrict__ Hg,
+                                                             const double *__restrict__ Ag, double *__restrict__ fac,
+                                                             int32_t *__restrict__ fstatus, int n, int m) {
+  __shared__ double lds[QPB * SLOT];
+  gi_group<MR, N16, FULL, false, false, false, false, 1>(lds, Hg, nullptr, Ag, nullptr, fac, nullptr, nullptr, fstatus,
+                                                         nullptr, n, m, 1, 0, 0.0, 0, nullptr, 0);
+}
+
+// qpb_solve_factored's form: gi_group with FM = 2, with or without equality rows
+template <int MR, bool N16, bool FULL, bool EQ, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_factored_kernel(
+    const double *__restrict__ facg, const double *__restrict__ fg, const double *__restrict__ bg,
+    double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg, int32_t *__restrict__ statg,
+    int32_t *__restrict__ itg, int n, int m, int meq, long long batch, int max_iter, double feas_tol) {
+  __shared__ double lds[QPB * SLOT];
+  static_assert(fct::layout(16, 16 * MR).mr == MR);
+  gi_group<MR, N16, FULL, false, EQ, true, false, 2>(lds, facg, fg, facg + fct::layout(n, m).A, bg, xg, lamg, actg,
+                                                     statg, itg, n, m, batch, max_iter, feas_tol, 0, nullptr,
+                                                     blockIdx.x, meq, 0, 0);
+}
+
 }  // namespace qpb
 
 // launcher used by qpb_api.hip
@@ -1053,6 +1195,36 @@ extern "C" hipError_t qpb_launch_gi_range(const qpb_desc *d, int meq, long long 
     hipLaunchKernelGGL((qpb::gi_dense_range_kernel<MR(), N16(), FULL(), qpb::kEqOcc>), dim3((unsigned)blocks),
                        dim3(64), 0, stream, H, f, A, bl, bu, x, lam, active, lower, status, iters, d->n, d->m, meq,
                        (long long)d->batch, max_iter, tol, strideH, strideA);
+  });
+  return hipGetLastError();
+}
+
+// qpb_factor_shared, n <= 16 and m <= 32: one launch of one workgroup
+extern "C" hipError_t qpb_launch_gi_factor(int n, int m, const double *H, const double *A, double *fac,
+                                           int32_t *fstatus, hipStream_t stream) {
+  qpb::row16::dispatch_form(n, m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_factor_kernel<MR(), N16(), FULL()>), dim3(1), dim3(64), 0, stream, H, A, fac,
+                       fstatus, n, m);
+  });
+  return hipGetLastError();
+}
+
+// qpb_solve_factored, n <= 16 and m <= 32: the six forms on a factor buffer,
+// plain (meq == 0) and EQ
+extern "C" hipError_t qpb_launch_gi_factored(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                             const double *b, double *x, double *lam, uint32_t *active,
+                                             int32_t *status, int32_t *iters, hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    if (meq > 0)
+      hipLaunchKernelGGL((qpb::gi_dense_factored_kernel<MR(), N16(), FULL(), true, qpb::kEqOcc>),
+                         dim3((unsigned)blocks), dim3(64), 0, stream, fac, f, b, x, lam, active, status, iters, d->n,
+                         d->m, meq, (long long)d->batch, max_iter, tol);
+    else
+      hipLaunchKernelGGL((qpb::gi_dense_factored_kernel<MR(), N16(), FULL(), false, 3>), dim3((unsigned)blocks),
+                         dim3(64), 0, stream, fac, f, b, x, lam, active, status, iters, d->n, d->m, 0,
+                         (long long)d->batch, max_iter, tol);
   });
   return hipGetLastError();
 }

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "qpb_common.h"
+#include "qpb_factor.h"  // the factor buffer of qpb_factor_shared / qpb_solve_factored
 #include "qpb_launch.h"  // with qpb.h
 
 namespace qpb {
@@ -110,6 +111,23 @@ struct RangeArgs {
   const double *bl;  // m per QP, or NULL: no row has a lower bound
   uint32_t *lower;   // ceil(m/32) words per QP, or NULL: not wanted
 };
+// The factor forms (qpb_factor.h has the buffer) ride in the same pack:
+// FactorOut (qpb_factor_shared): ONE problem (batch 1, no f and no b), the
+// kernel's own load and sweep, then L (as packed in LDS), D, the rows' norms,
+// A and what the set-up found go to the buffer, and nothing else runs.
+// FactorIn (qpb_solve_factored, plain or EQ): no H or A is loaded and nothing
+// is staged or swept -- L is copied flat into LDS, the lane's row of D comes
+// from the buffer with 16-byte loads at consecutive addresses, thr from the
+// stored |a_r| and dn from the stored |D_r|^2; y = L^-1 f is the lane-parallel
+// forward substitution of the finish, and s = b + D y the line the sweep ends
+// with.  From there on the code is the other forms'.
+struct FactorOut {
+  double *fac;
+  int32_t *fstatus;  // may be NULL
+};
+struct FactorIn {
+  const double *fac;
+};
 template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false,
           class... RGA>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
@@ -117,7 +135,11 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
     double feas_tol, unsigned long long *__restrict__ dbg = nullptr, RGA... rga) {
-  constexpr bool RG = sizeof...(RGA) != 0;
+  constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...);
+  constexpr bool FO = (std::is_same_v<RGA, FactorOut> || ...), FI = (std::is_same_v<RGA, FactorIn> || ...);
+  static_assert(sizeof...(RGA) <= 1 && (sizeof...(RGA) == 0 || RG || FO || FI), "one trailing argument at most");
+  static_assert(!(FO || FI) || (!(STAMP || REDO || BOX || SH) && (!FO || !EQ)),
+                "the factor forms are the plain or the EQ kernel's");
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
   static_assert(!SH || !(STAMP || REDO || BOX), "the shared form is the plain or the EQ kernel's");
   static_assert(!RG || (EQ && SH && (std::is_same_v<RGA, RangeArgs> && ...) && sizeof...(RGA) == 1),
@@ -130,6 +152,15 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const RangeArgs ra = [](RangeArgs a) { return a; }(rga...);
     blg = ra.bl;
     lowg = ra.lower;
+  }
+  [[maybe_unused]] const double *facg = nullptr;  // FI: the buffer
+  [[maybe_unused]] double *faco = nullptr;        // FO: the buffer, and where the finding goes
+  [[maybe_unused]] int32_t *fstat = nullptr;
+  if constexpr (FI) facg = [](FactorIn a) { return a; }(rga...).fac;
+  if constexpr (FO) {
+    const FactorOut fo = [](FactorOut a) { return a; }(rga...);
+    faco = fo.fac;
+    fstat = fo.fstatus;
   }
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -153,9 +184,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double *xch = R;             // the exchange row: R's column 0, never read by the back substitution
   double *xsd = lds + OFF_X;   // s_p, |D[p,:]|^2
 
-  const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
+  const double *Hq = FI ? facg : SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
   // BOX: Ag = lb, bg = ub (n per QP, either may be NULL), m = 2n
-  const double *Aq = BOX      ? Hq
+  const double *Aq = FI       ? facg + fct::layout(n, m).A
+                     : BOX    ? Hq
                      : m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n)
                              : Hq;
   const double *bq = BOX ? Hq : m > 0 ? bg + g * (long long)m : Hq;
@@ -185,11 +217,37 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     // bu and bl, each NULL when no row has that side
     bv = bg ? bq[rowok ? l : 0] : kInf;
     rg.lo[0] = blg ? blg[g * (long long)m + (rowok ? l : 0)] : -kInf;
+  } else if constexpr (FO) {
+    bv = 0.0;
   } else {
     bv = bq[rowok ? l : 0];
   }
-  const double fv = fg[g * n + (l < n ? l : 0)];
-  {
+  double fv = 0.0;
+  if constexpr (!FO) fv = fg[g * n + (l < n ? l : 0)];
+  // FI: |a_l|^2, |a_l|, |D_l|^2 and the positive-definite flag from the buffer
+  [[maybe_unused]] double f_an2 = 0.0, f_an = 0.0, f_dn = 0.0;
+  [[maybe_unused]] bool fspd = true;
+  constexpr int oFL = fct::kHdr, oFD = oFL + L_SIZE, oFN = oFD + 64 * NP, oFA = oFN + 3 * 64;
+  static_assert(fct::layout(NP, 64).D == oFD && fct::layout(NP, 64).an2 == oFN && fct::layout(17, 0).A == oFA);
+  if constexpr (FI) {
+    fspd = facg[0] != (double)QPB_NOT_SPD;
+#pragma unroll
+    for (int i = 0; i < (L_SIZE + 63) / 64; ++i) {
+      const int e = i * 64 + l;
+      if (e < L_SIZE) Lp[e] = facg[oFL + e];
+    }
+#pragma unroll
+    for (int t = 0; t < NH; ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&facg[oFD + (t * 64 + l) * 2]);
+      E[2 * t] = v.x;
+      E[2 * t + 1] = v.y;
+    }
+    f_an2 = facg[oFN + l];
+    f_an = facg[oFN + 64 + l];
+    f_dn = facg[oFN + 128 + l];
+    wave_lds_sync();
+  }
+  if constexpr (!FI) {
     constexpr int RST = NP + 2;  // staged row stride
     const int nn = n * n, h0 = (m < NP ? m : NP) * n, h1 = m * n - h0;  // A rows 0-31 | 32-63
     double hv[16], av[2][16];
@@ -274,7 +332,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   }
 
   clk.tick(0);  // load
-  const double nrm2 = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
+  double nrm2;
+  if constexpr (FI) nrm2 = f_an2;
+  else nrm2 = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
   [[maybe_unused]] double rg_b = 0.0, rg_thr = 0.0;
   [[maybe_unused]] bool rg_inf = false;
   if constexpr (RG) {
@@ -306,8 +366,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   }
   const double bl = RG ? rg_b : rowok ? bv : 0.0;
   // violated: s / |D row| < -tol (1 + |b| / |D row|), i.e. s < -tol (|D row| + |b|)
-  const double thr =
-      RG ? rg_thr : (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
+  double thr;
+  if constexpr (FI) thr = (rowok && nrm2 > 0.0) ? -feas_tol * (f_an + __builtin_fabs(bl)) : -kInf;
+  else thr = RG ? rg_thr : (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
   const bool infeasible0 =
       RG ? rg_inf : wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
   // a row of A with a NaN entry or an overflowing norm fails every comparison
@@ -333,7 +394,30 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   const bool hi = l >= NP;
   const int r = l & (NP - 1), li = l & (NH - 1);
   double *pv = R + 2 * NP;  // R is free until the loop (R[0..31]: y capture)
-  unroll<NP>([&](auto K) {
+  if constexpr (FI) {
+    // y = L^-1 f from the stored L, lane-parallel as in the finish: step k
+    // broadcasts the finished component from lane k, every lane updates its
+    // own (entries past the diagonal sit inside L's packed storage and only
+    // update dead values), and y_k is captured where the sweep leaves it
+    (void)hi, (void)r, (void)pv;
+    spd = fspd;
+    const double invd = r < n ? rcp(Lp[lrow(r) + r]) : 0.0;
+    double Lrow[NP];
+    unroll<NP>([&](auto K) {
+      constexpr int kk = K;
+      Lrow[kk] = Lp[lrow(r) + kk];
+    });
+    wave_lds_sync();
+    unroll<NP>([&](auto K) {
+      constexpr int kk = K;
+      if (kk < n) {
+        const double yk = readlane_d(ya * invd, kk);
+        ya = __builtin_fma(-Lrow[kk], yk, ya);
+        R[kk] = yk;
+      }
+    });
+  }
+  if constexpr (!FI) unroll<NP>([&](auto K) {
     constexpr int k = K, kh = k / NH, kk = k % NH;
     if (k >= n) return;  // wave-uniform: padded columns stay zero
     __builtin_amdgcn_sched_barrier(0);
@@ -392,12 +476,12 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // L -> LDS, packed rows: the upper half first, then the lower half, each in
   // descending column order.  A dead entry (column j > r) lands in a later row
   // at a smaller column, whose owner writes it afterwards (in-order DS).
-  unroll<NH>([&](auto J) {
+  if constexpr (!FI) unroll<NH>([&](auto J) {
     constexpr int jj = NH - 1 - J;
     if (hi) Lp[lrow(r) + NH + jj <= L_SIZE - 1 ? lrow(r) + NH + jj : L_SIZE - 1] = Lr[jj];
     wave_lds_sync();
   });
-  unroll<NH>([&](auto J) {
+  if constexpr (!FI) unroll<NH>([&](auto J) {
     constexpr int jj = NH - 1 - J;
     if (!hi) Lp[lrow(r) + jj] = Lr[jj];
     wave_lds_sync();
@@ -405,7 +489,29 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // y replicated: s = b + D y, |D row|^2
   wave_lds_sync();
   double s = bl + bdot(E, R[li], R[NH + li]);
-  const double dn = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
+  double dn;
+  if constexpr (FI) dn = f_dn;
+  else dn = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
+  if constexpr (FO) {
+    // ---- the factor kernel ends here (one workgroup, g == 0): the buffer
+    const int found = !spd ? QPB_NOT_SPD : nan0 ? QPB_NUMERICAL : QPB_OK;
+    if (l < fct::kHdr)
+      faco[l] = l == 0 ? (double)found : l == 1 ? (double)n : l == 2 ? (double)m : l == 3 ? (double)NP : 0.0;
+    if (l == 0 && fstat) fstat[0] = found;
+#pragma unroll
+    for (int i = 0; i < (L_SIZE + 63) / 64; ++i) {
+      const int e = i * 64 + l;
+      if (e < L_SIZE) faco[oFL + e] = Lp[e];
+    }
+#pragma unroll
+    for (int t = 0; t < NH; ++t)
+      *reinterpret_cast<double2 *>(&faco[oFD + (t * 64 + l) * 2]) = make_double2(E[2 * t], E[2 * t + 1]);
+    faco[oFN + l] = nrm2;
+    faco[oFN + 64 + l] = nrm2 > 0.0 ? nrm2 * rsq(nrm2) : 0.0;
+    faco[oFN + 128 + l] = dn;
+    for (int i = l; i < m * n; i += 64) faco[oFA + i] = Aq[i];
+    return;
+  }
   float fn2 = (float)dn;  // |D[l, q:]|^2, the free part of the row (scale of the selection key)
 
   // ------------------------------------------------------ active-set loop
@@ -951,5 +1057,31 @@ extern "C" hipError_t qpb_launch_gi_wave_range(const qpb_desc *d, int meq, long 
   hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, true, qpb::wv::RangeArgs>),
                      dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, bu, x, lam, active, status, iters, d->n,
                      mm, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::RangeArgs{bl, lower});
+  return hipGetLastError();
+}
+
+// qpb_factor_shared for the n <= 32, m <= 64 class: one launch of one wavefront
+extern "C" hipError_t qpb_launch_gi_wave_factor(int n, int m, const double *H, const double *A, double *fac,
+                                                int32_t *fstatus, hipStream_t stream) {
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, false, false, qpb::wv::FactorOut>), dim3(1),
+                     dim3(64), 0, stream, H, nullptr, A, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n, m, 1LL,
+                     0, 0.0, nullptr, qpb::wv::FactorOut{fac, fstatus});
+  return hipGetLastError();
+}
+
+// qpb_solve_factored for the n <= 32, m <= 64 class, plain (meq == 0) or EQ
+extern "C" hipError_t qpb_launch_gi_wave_factored(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                                  const double *b, double *x, double *lam, uint32_t *active,
+                                                  int32_t *status, int32_t *iters, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  if (meq > 0)
+    hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, false, qpb::wv::FactorIn>),
+                       dim3((unsigned)d->batch), dim3(64), 0, stream, fac, f, fac, b, x, lam, active, status, iters,
+                       d->n, d->m | (meq << qpb::wv::kEqShift), (long long)d->batch, max_iter, tol, nullptr,
+                       qpb::wv::FactorIn{fac});
+  else
+    hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, false, false, qpb::wv::FactorIn>),
+                       dim3((unsigned)d->batch), dim3(64), 0, stream, fac, f, fac, b, x, lam, active, status, iters,
+                       d->n, d->m, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::FactorIn{fac});
   return hipGetLastError();
 }

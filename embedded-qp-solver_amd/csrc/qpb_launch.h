@@ -58,6 +58,18 @@ typedef hipError_t qpb_gi_range_launcher(const qpb_desc *d, int meq, long long s
                                          int32_t *status, int32_t *iters, hipStream_t stream);
 QPB_LAUNCHER qpb_gi_range_launcher qpb_launch_gi_range,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_wave_range;                            // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_factor_shared: ONE H (n x n) and ONE A (m x n, NULL at m == 0) into the
+// class's factor buffer (qpb_factor.h), one small launch; fstatus may be NULL
+typedef hipError_t qpb_gi_factor_launcher(int n, int m, const double *H, const double *A, double *fac,
+                                          int32_t *fstatus, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_factor_launcher qpb_launch_gi_factor,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_factor;                             // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_factored: the solve on such a buffer; meq == 0 is the plain form, meq > 0 the EQ form
+typedef hipError_t qpb_gi_factored_launcher(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                            const double *b, double *x, double *lam, uint32_t *active,
+                                            int32_t *status, int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_factored_launcher qpb_launch_gi_factored,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_factored;                               // n <= 32, m <= 64 (qpb_gi_wave.hip)
 // qpb_solve_shared_backward, pass 1: qpb_launch_kkt_bwd with the same strides
 // (gH / gA NULL where pass 2 sums the gradient)
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long strideH, long long strideA,

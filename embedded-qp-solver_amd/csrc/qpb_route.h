@@ -152,6 +152,24 @@ static_assert(route_shared(kSharedMaxN, kSharedMaxM).step > 0 && route_shared(kS
 static_assert(route_shared_bwd(kSharedMaxN, kSharedMaxM).step > 0 && route_shared_bwd(kSharedMaxN + 1, 1).step == 0 &&
               route_shared_bwd(1, kSharedMaxM + 1).step == 0);
 
+// qpb_factor_shared and qpb_solve_factored: route_shared's classes, whose
+// factor kernel writes and whose factored form reads the class's own layout of
+// the buffer (qpb_factor.h decides the class by the same two limits); above
+// them there is neither: step 0, and the calls are unsupported.
+constexpr Route route_factored(int n, int m) {
+  const Route r = route_shared(n, m);
+  return {r.kernel, r.step};
+}
+constexpr int kFactoredMaxN = kSharedMaxN, kFactoredMaxM = kSharedMaxM;
+
+static_assert(route_factored(16, 32).kernel == Kernel::gi_dense && route_factored(1, 0).kernel == Kernel::gi_dense);
+static_assert(route_factored(16, 33).kernel == Kernel::gi_wave && route_factored(17, 0).kernel == Kernel::gi_wave &&
+              route_factored(32, 64).kernel == Kernel::gi_wave);
+static_assert(route_factored(16, 32).step == 1LL << 27 && route_factored(32, 64).step == 1LL << 25);
+static_assert(route_factored(33, 0).step == 0 && route_factored(16, 65).step == 0 && route_factored(128, 256).step == 0);
+static_assert(route_factored(kFactoredMaxN, kFactoredMaxM).step > 0 && route_factored(kFactoredMaxN + 1, 1).step == 0 &&
+              route_factored(1, kFactoredMaxM + 1).step == 0);
+
 // qpb_solve_range with m > 0: the RG forms of the two wavefront-level classes,
 // whatever meq and the shared bits (the forms take both at run time); above
 // them -- the Gram class -- there is no range form yet: step 0, and the call is

@@ -84,6 +84,16 @@ _lib.qpb_solve_shared.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c
 _lib.qpb_solve_shared.restype = ctypes.c_int
 _lib.qpb_solve_shared_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 9
 _lib.qpb_solve_shared_host.restype = ctypes.c_int
+_lib.qpb_factor_doubles.argtypes = [ctypes.c_int32, ctypes.c_int32]
+_lib.qpb_factor_doubles.restype = ctypes.c_int64
+_lib.qpb_factor_shared.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_vp] * 5
+_lib.qpb_factor_shared.restype = ctypes.c_int
+_lib.qpb_factor_shared_host.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_vp] * 4
+_lib.qpb_factor_shared_host.restype = ctypes.c_int
+_lib.qpb_solve_factored.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 9
+_lib.qpb_solve_factored.restype = ctypes.c_int
+_lib.qpb_solve_factored_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 8
+_lib.qpb_solve_factored_host.restype = ctypes.c_int
 _lib.qpb_solve_shared_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 12
 _lib.qpb_solve_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_shared_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
@@ -431,6 +441,121 @@ def solve_shared_host(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, 
     rc = _lib.qpb_solve_shared_host(ctypes.byref(d), int(meq), shared, p(H), p(f), p(A) if m else None,
                                     p(b) if m else None, p(x), p(lam), p(act), p(st), p(it))
     _check(rc, "qpb_solve_shared_host")
+    return Solution(x, lam, act, st, it)
+
+
+class SharedFactor(NamedTuple):
+    """One shared H and A, factored once (qpb_factor_shared): the input of ``solve_factored``."""
+    fac: object     # (factor_doubles(n, m),) float64: L, D = A L^-T, the rows' norms, A (layout internal)
+    n: int
+    m: int
+    status: object  # (1,) int32: OK, NOT_SPD, or NUMERICAL for a NaN or overflowing row of A
+
+
+def factor_doubles(n: int, m: int) -> int:
+    """Doubles a factor buffer for (n, m) holds (qpb_factor_doubles; n <= 32, m <= 64)."""
+    k = int(_lib.qpb_factor_doubles(int(n), int(m)))
+    if k < 0:
+        _check(k, "qpb_factor_doubles")
+    return k
+
+
+def factor_shared(H, A=None, *, stream=None) -> SharedFactor:
+    """Factor ONE H (n, n) and ONE A (m, n) for a whole batch, once
+    (qpb_factor_shared): torch CUDA float64 tensors, one small launch,
+    asynchronous on ``stream``.  The result goes to ``solve_factored`` any
+    number of times -- an MPC loop factors once per model and solves every tick.
+    n <= 32 and m <= 64."""
+    import torch
+    if not H.is_cuda:
+        raise ValueError("qpb.factor_shared expects CUDA (HIP) tensors; use factor_shared_host for numpy")
+    m = 0 if A is None else A.shape[0]
+    for t in (H,) + ((A,) if m else ()):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+        if t.device != H.device:
+            raise ValueError("the inputs must live on the same CUDA device")
+    n = H.shape[-1]
+    if tuple(H.shape) != (n, n) or (m and tuple(A.shape) != (m, n)):
+        raise ValueError("shape mismatch: H must be (n, n) and A (m, n)")
+    fac = torch.empty((factor_doubles(n, m),), dtype=torch.float64, device=H.device)
+    status = torch.empty((1,), dtype=torch.int32, device=H.device)
+    rc = _lib.qpb_factor_shared(n, m, _ptr(H), _ptr(A) if m else None, _ptr(fac), _ptr(status), _stream_ptr(stream))
+    _check(rc, "qpb_factor_shared")
+    return SharedFactor(fac, n, m, status)
+
+
+def solve_factored(F: SharedFactor, f, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                   out: Solution | None = None, stream=None) -> Solution:
+    """``solve_shared`` with a 2-D H and A, without the per-QP set-up
+    (qpb_solve_factored): ``F`` is ``factor_shared(H, A)``, f (B, n) and b (B, m)
+    are per QP.  The contract is ``solve_shared``'s except that x and lam may
+    differ from it by rounding and ``iters`` need not be the same."""
+    import torch
+    if not (f.is_cuda and F.fac.is_cuda):
+        raise ValueError("qpb.solve_factored expects CUDA (HIP) tensors; use solve_factored_host for numpy")
+    n, m = int(F.n), int(F.m)
+    for t in (f,) + ((b,) if m else ()):
+        if t is None or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+        if t.device != F.fac.device:
+            raise ValueError("the inputs must live on the factor's CUDA device")
+    if f.dim() != 2 or f.shape[1] != n or (m and tuple(b.shape) != (f.shape[0], m)) or (not m and b is not None
+                                                                                        and b.numel()):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    if F.fac.dtype != torch.float64 or tuple(F.fac.shape) != (factor_doubles(n, m),) or not F.fac.is_contiguous():
+        raise ValueError(f"the factor buffer is not one for n={n}, m={m}")
+    B = f.shape[0]
+    if out is None:
+        out = _empty_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_factored(ctypes.byref(d), int(meq), _ptr(F.fac), _ptr(f), _ptr(b) if m else None,
+                                 _ptr(out.x), _ptr(out.lam), _ptr(out.active), _ptr(out.status), _ptr(out.iters),
+                                 _stream_ptr(stream))
+    _check(rc, "qpb_solve_factored")
+    return out
+
+
+def factor_shared_host(H, A=None) -> SharedFactor:
+    """numpy in / numpy out (qpb_factor_shared_host): ``factor_shared`` with host arrays."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    m = 0 if A is None else A.shape[0]
+    n = H.shape[-1]
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+    if H.shape != (n, n) or (m and A.shape != (m, n)):
+        raise ValueError("shape mismatch: H must be (n, n) and A (m, n)")
+    fac = np.zeros(factor_doubles(n, m))
+    st = np.zeros(1, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_factor_shared_host(n, m, p(H), p(A) if m else None, p(fac), p(st))
+    _check(rc, "qpb_factor_shared_host")
+    return SharedFactor(fac, n, m, st)
+
+
+def solve_factored_host(F: SharedFactor, f, b=None, meq: int = 0, *, max_iter: int = 0,
+                        feas_tol: float = 0.0) -> Solution:
+    """numpy in / numpy out (qpb_solve_factored_host): ``solve_factored`` with host arrays."""
+    import numpy as np
+    n, m = int(F.n), int(F.m)
+    fac = np.ascontiguousarray(F.fac, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if m:
+        b = np.ascontiguousarray(b, dtype=np.float64)
+    B = f.shape[0]
+    if f.shape != (B, n) or (m and b.shape != (B, m)) or fac.shape != (factor_doubles(n, m),):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, (m + 31) // 32), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_factored_host(ctypes.byref(d), int(meq), p(fac), p(f), p(b) if m else None, p(x), p(lam),
+                                      p(act), p(st), p(it))
+    _check(rc, "qpb_solve_factored_host")
     return Solution(x, lam, act, st, it)
 
 

@@ -12,7 +12,11 @@ solution's active set, on the GPU).  This module imports torch at the top;
 A 2-D ``H`` (n, n) and / or ``A`` (m, n) is ONE matrix for the whole batch --
 the weights of a QP layer, with f and b from the network's input: the solve is
 ``qpb.solve_shared``, the backward ``qpb.solve_shared_backward``, ``H.grad``
-is (n, n), and no (B, n, n) or (B, m, n) tensor is ever allocated.
+is (n, n), and no (B, n, n) or (B, m, n) tensor is ever allocated.  With
+``prefactor=True`` (a 2-D H and, when there are rows, a 2-D A) the forward
+factors the two once, ``qpb.factor_shared``, and solves with
+``qpb.solve_factored``: the per-QP set-up is gone from the forward; the
+backward is the same ``qpb.solve_shared_backward``.
 
 ``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
 and ub (``qpb.solve_box_backward``, n <= 32).
@@ -33,12 +37,14 @@ class QPFunction(torch.autograd.Function):
     """x*(H, f, A, b) of min 1/2 x'Hx + f'x s.t. A[:meq] x = b[:meq], A[meq:] x <= b[meq:]."""
 
     @staticmethod
-    def forward(ctx, H, f, A, b, meq, max_iter, feas_tol):
+    def forward(ctx, H, f, A, b, meq, max_iter, feas_tol, prefactor):
         H, f = H.contiguous(), f.contiguous()
         if A is not None:
             A, b = A.contiguous(), b.contiguous()
         ctx.shared = H.dim() == 2 or (A is not None and A.dim() == 2)
-        if ctx.shared:
+        if prefactor:
+            sol = qpb.solve_factored(qpb.factor_shared(H, A), f, b, meq, max_iter=max_iter, feas_tol=feas_tol)
+        elif ctx.shared:
             sol = qpb.solve_shared(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
         else:
             sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol) if A is not None \
@@ -53,12 +59,12 @@ class QPFunction(torch.autograd.Function):
         H, A, x, lam, active, status = ctx.saved_tensors
         wanted = [k for k, w in zip("HfAb", ctx.needs_input_grad[:4]) if w and (ctx.has_rows or k in "Hf")]
         if not wanted:
-            return (None,) * 7
+            return (None,) * 8
         sol = qpb.Solution(x, lam, active, status, None)
         # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
         backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
         gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
-        return gH, gf, gA, gb, None, None, None
+        return gH, gf, gA, gb, None, None, None, None
 
 
 class BoxQPFunction(torch.autograd.Function):
@@ -154,7 +160,7 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.
     return BoxQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol))
 
 
-def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):
     """Differentiable batched solve: returns ``(x, status)``; ``x`` carries
     gradients to whichever of H, f, A and b require them, ``status`` (int32 per
     QP) is not differentiable.  QPs whose status is not OK contribute zero
@@ -162,5 +168,12 @@ def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: fl
     The forward solves every shape ``qpb.solve_eq`` does; the backward needs
     n <= 32 and m <= 64.  H (n, n) and / or A (m, n) may be 2-D: one matrix
     shared by the batch (n <= 32, m <= 64), whose gradient is the sum over the
-    batch, computed without a per-QP copy."""
-    return QPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol))
+    batch, computed without a per-QP copy.  ``prefactor=True`` needs a 2-D H
+    and (when there are rows) a 2-D A, else ValueError: the forward factors
+    them once (``qpb.factor_shared``) and solves with ``qpb.solve_factored``,
+    whose x may differ from the default's by rounding; the backward is the
+    same.  The default is today's call, bit for bit."""
+    if prefactor:
+        if H.dim() != 2 or (A is not None and A.dim() != 2):
+            raise ValueError("prefactor=True needs a 2-D H (n, n) and, with rows, a 2-D A (m, n): one matrix for the batch")
+    return QPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol), bool(prefactor))

@@ -15,6 +15,7 @@
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
+ *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
@@ -320,10 +321,9 @@ int qpb_solve_backward_host(const qpb_desc *desc, const double *H,
  * are looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
  * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
  * with m <= 64.  Follow-ups: the n <= 128 Gram class (qpb_gi_gram.hip) has no
- * shared form; a shared-H qpb_solve_box; and factoring a shared H ONCE -- with
- * one H, L is the same for every QP and with one A so is D = A L^-T, which
- * this version recomputes per QP on purpose, so that bit-for-bit equality with
- * qpb_solve_eq is its test.
+ * shared form; a shared-H qpb_solve_box.  This call factors H per QP on purpose,
+ * so that bit-for-bit equality with qpb_solve_eq is its test; factoring a
+ * shared H ONCE is qpb_factor_shared and qpb_solve_factored below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_shared(const qpb_desc *desc, int32_t meq, int32_t shared,
 		     const double *H, const double *f, const double *A,
@@ -335,6 +335,79 @@ int qpb_solve_shared_host(const qpb_desc *desc, int32_t meq, int32_t shared,
 			  const double *H, const double *f, const double *A,
 			  const double *b, double *x, double *lam,
 			  uint32_t *active, int32_t *status, int32_t *iters);
+
+/* One H and one A for the whole batch, factored ONCE.  With both shared, the
+ * set-up of every QP -- H = L L^T and D = A L^-T -- is the same numbers;
+ * qpb_factor_shared computes them once into a factor buffer, and
+ * qpb_solve_factored starts every QP from it: what is left per QP is
+ * y = L^-1 f and s = b + D y.  An MPC loop factors once per model and solves
+ * every tick; a QP layer factors once per forward pass.
+ *
+ * The buffer `fac` is self-contained: L, D, per row |a_r|^2, |a_r| and
+ * |D_r|^2, a copy of A (the x recovery re-reads the active rows) and the two
+ * findings of the set-up that do not depend on b, a non-SPD H and a NaN or
+ * overflowing row of A.  The solve takes neither H nor A.  Its layout is
+ * internal (csrc/qpb_factor.h) and belongs to one (n, m): a
+ * buffer made for another shape is the caller's error, like any wrongly sized
+ * array.  `fac` must be 16-byte aligned (hipMalloc's and torch's allocations
+ * are), else QPB_ERR_INVALID_ARG. */
+
+/* doubles a factor buffer for (n, m) holds; < 0: a qpb_error (n < 1, m < 0:
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64: QPB_ERR_UNSUPPORTED).  Pure host
+ * arithmetic. */
+int64_t qpb_factor_doubles(int32_t n, int32_t m);
+
+/* Factor ONE H (n x n) and ONE A (m x n; NULL with m == 0) into `fac`
+ * (qpb_factor_doubles(n, m) doubles, device).  One small launch, asynchronous
+ * on `stream`: a solve queued behind it on the same stream needs no host
+ * synchronisation.  fstatus (one int32, device, may be NULL): QPB_OK,
+ * QPB_NOT_SPD, or QPB_NUMERICAL for a row of A with a NaN entry or a non-finite
+ * squared norm.  L and D are the values the unfactored kernels compute: each
+ * class's factor kernel runs that class's own load and sweep.
+ * Errors, in order: n < 1 or m < 0 QPB_ERR_INVALID_ARG; n > 32 or m > 64
+ * QPB_ERR_UNSUPPORTED; H or fac missing, or A missing with m > 0,
+ * QPB_ERR_INVALID_ARG; a missing device last. */
+int qpb_factor_shared(int32_t n, int32_t m, const double *H, const double *A,
+		      double *fac, int32_t *fstatus, void *stream);
+
+/* Same with host pointers; fac (host) receives the buffer. */
+int qpb_factor_shared_host(int32_t n, int32_t m, const double *H,
+			   const double *A, double *fac, int32_t *fstatus);
+
+/* qpb_solve_shared(shared = QPB_SHARED_H | QPB_SHARED_A) without the per-QP
+ * set-up, on a buffer of qpb_factor_shared for (desc->n, desc->m).  The
+ * contract is that call's: what is written for every status, a NaN b as an
+ * absent row, the equality rows' rules (rows 0 .. meq-1), lam >= 0 exactly on
+ * the rows >= meq, the default max_iter 4 (n + m) + 8, feas_tol per call; a
+ * QP's outputs depend on its own f and b and on fac only, not on the batch
+ * size or its position in the batch.  Two things differ.  The outputs are not
+ * bit for bit qpb_solve_eq's: L and D are the same numbers, but s = b + D y is
+ * formed from them and no longer inside the sweep, so x and lam differ by
+ * rounding; on a non-degenerate QP status and active are the same.  And iters
+ * may differ from the unfactored solve's.
+ * A buffer whose H was not SPD gives every QP QPB_NOT_SPD, one with a NaN row
+ * of A gives every QP QPB_NUMERICAL; a zero row of A is judged against each
+ * QP's own b.  The buffer is only read: any number of solves, on any streams,
+ * may use it at once.
+ * Errors, in order: the descriptor as qpb_solve; meq < 0 or desc->flags != 0
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64 QPB_ERR_UNSUPPORTED; meq > m
+ * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
+ * missing pointers QPB_ERR_INVALID_ARG (fac, f, x and status always; b, lam and
+ * active with m > 0; iters may be NULL); a missing device last.
+ * Follow-ups: a factored qpb_solve_shared_backward (kkt_bwd re-factors H and
+ * re-forms A_W L^-T per QP), a factored range form, and a shared H with a
+ * per-QP A.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_factored(const qpb_desc *desc, int32_t meq, const double *fac,
+		       const double *f, const double *b, double *x, double *lam,
+		       uint32_t *active, int32_t *status, int32_t *iters,
+		       void *stream);
+
+/* Same with host pointers (fac included: the call uploads it). */
+int qpb_solve_factored_host(const qpb_desc *desc, int32_t meq,
+			    const double *fac, const double *f, const double *b,
+			    double *x, double *lam, uint32_t *active,
+			    int32_t *status, int32_t *iters);
 
 /* qpb_solve_backward with a shared H and / or A: the gradient of a shared
  * operand is ONE matrix, the sum over the batch.
