@@ -117,6 +117,12 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 //      forward substitution and s = b + D y, n (1 + MR) DPP-fused FMAs in place
 //      of the sweep.  From there on -- the loop and the outputs -- the code is
 //      the other forms', plain and EQ.
+//      With RG (qpb_solve_range_factored): bu and bl are loaded as in the range
+//      form; row_norms takes |a_r|^2 and |a_r| from the buffer, so the thresholds
+//      are the unfactored range form's bit for bit, and a row whose only bound
+//      is the lower one negates the lane's row of D -- the negated row of A would
+//      have swept into exactly that -- before s is formed.  The loop and the
+//      outputs are the range form's.
 template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false, int FM = 0>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
@@ -129,7 +135,8 @@ __device__ __forceinline__ void gi_group(
   static_assert(!FULL || N16, "FULL implies n == 16");
   static_assert(!RG || (EQ && SH), "the range form is built on the EQ and the shared forms");
   static_assert(!SH || !STAMP, "the shared form has no stamped build");
-  static_assert(FM == 0 || (!STAMP && !RG && (FM == 1 ? !EQ && !SH : SH)), "the factor forms are plain, EQ or SH ones");
+  static_assert(FM == 0 || (!STAMP && (FM == 1 ? !EQ && !SH && !RG : SH)),
+                "the factor forms are plain, EQ or SH ones; the range form has a factored solve only");
   SectionClock<STAMP> clk;
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -245,7 +252,10 @@ __device__ __forceinline__ void gi_group(
       const double hi = has_hi ? bv[r] : kInf, lo = has_lo ? rg.lo[r] : -kInf;
       const double beta = __builtin_fmax(has_hi ? __builtin_fabs(hi) : 0.0, has_lo ? __builtin_fabs(lo) : 0.0);
       const bool pre = ok && has_lo && !has_hi;
-      const double nrm = !(nrm2 <= 0.0) ? nrm2 * rsq1(nrm2) : 0.0;
+      // (FM == 2: the stored |a_r| is this very product, 0 for a zero row)
+      double nrm;
+      if constexpr (FM == 2) nrm = !(nrm2 <= 0.0) ? an1[r] : 0.0;
+      else nrm = !(nrm2 <= 0.0) ? nrm2 * rsq1(nrm2) : 0.0;
       rg.low[r] = pre;
       rg.w[r] = (ok && has_hi && has_lo) ? hi - lo : kInf;
       bl[r] = ok ? (pre ? -lo : hi) : 0.0;
@@ -1107,6 +1117,20 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_factored_kernel(
                                                      blockIdx.x, meq, 0, 0);
 }
 
+// qpb_solve_range_factored's form: gi_group with RG and FM = 2 (meq an argument)
+template <int MR, bool N16, bool FULL, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_range_factored_kernel(
+    const double *__restrict__ facg, const double *__restrict__ fg, const double *__restrict__ blg,
+    const double *__restrict__ bug, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
+    uint32_t *__restrict__ lowg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, int meq,
+    long long batch, int max_iter, double feas_tol) {
+  __shared__ double lds[QPB * SLOT];
+  static_assert(fct::layout(16, 16 * MR).mr == MR);
+  gi_group<MR, N16, FULL, false, true, true, true, 2>(lds, facg, fg, facg + fct::layout(n, m).A, bug, xg, lamg, actg,
+                                                      statg, itg, n, m, batch, max_iter, feas_tol, 0, nullptr,
+                                                      blockIdx.x, meq, 0, 0, blg, lowg);
+}
+
 }  // namespace qpb
 
 // launcher used by qpb_api.hip
@@ -1225,6 +1249,22 @@ extern "C" hipError_t qpb_launch_gi_factored(const qpb_desc *d, int meq, const d
       hipLaunchKernelGGL((qpb::gi_dense_factored_kernel<MR(), N16(), FULL(), false, 3>), dim3((unsigned)blocks),
                          dim3(64), 0, stream, fac, f, b, x, lam, active, status, iters, d->n, d->m, 0,
                          (long long)d->batch, max_iter, tol);
+  });
+  return hipGetLastError();
+}
+
+// qpb_solve_range_factored, n <= 16 and 1 <= m <= 32: the six forms with
+// two-sided rows and equality rows 0 .. meq-1 on a factor buffer
+extern "C" hipError_t qpb_launch_gi_range_factored(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                                   const double *bl, const double *bu, double *x, double *lam,
+                                                   uint32_t *active, uint32_t *lower, int32_t *status, int32_t *iters,
+                                                   hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_range_factored_kernel<MR(), N16(), FULL(), qpb::kEqOcc>),
+                       dim3((unsigned)blocks), dim3(64), 0, stream, fac, f, bl, bu, x, lam, active, lower, status,
+                       iters, d->n, d->m, meq, (long long)d->batch, max_iter, tol);
   });
   return hipGetLastError();
 }

@@ -128,6 +128,17 @@ struct FactorOut {
 struct FactorIn {
   const double *fac;
 };
+// RangeFactorIn (qpb_solve_range_factored): FactorIn's load together with
+// RangeArgs' two pointers, on the EQ form (no SH: the buffer stands for H and A).
+// The RG set-up takes |a_l|^2 and |a_l| from the buffer, so its thresholds are
+// the unfactored range form's bit for bit; a row whose only bound is the lower
+// one negates the lane's row of D -- what its negated row of A would have swept
+// into -- before s = b + D y.  The loop and the outputs are the range form's.
+struct RangeFactorIn {
+  const double *fac;
+  const double *bl;  // as RangeArgs
+  uint32_t *lower;
+};
 template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false,
           class... RGA>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
@@ -135,28 +146,29 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
     double feas_tol, unsigned long long *__restrict__ dbg = nullptr, RGA... rga) {
-  constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...);
-  constexpr bool FO = (std::is_same_v<RGA, FactorOut> || ...), FI = (std::is_same_v<RGA, FactorIn> || ...);
+  constexpr bool RF = (std::is_same_v<RGA, RangeFactorIn> || ...);
+  constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...) || RF;
+  constexpr bool FO = (std::is_same_v<RGA, FactorOut> || ...), FI = (std::is_same_v<RGA, FactorIn> || ...) || RF;
   static_assert(sizeof...(RGA) <= 1 && (sizeof...(RGA) == 0 || RG || FO || FI), "one trailing argument at most");
   static_assert(!(FO || FI) || (!(STAMP || REDO || BOX || SH) && (!FO || !EQ)),
                 "the factor forms are the plain or the EQ kernel's");
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
   static_assert(!SH || !(STAMP || REDO || BOX), "the shared form is the plain or the EQ kernel's");
-  static_assert(!RG || (EQ && SH && (std::is_same_v<RGA, RangeArgs> && ...) && sizeof...(RGA) == 1),
-                "the range form is built on the EQ and the shared forms and takes one RangeArgs");
+  static_assert(!RG || (EQ && SH != RF && sizeof...(RGA) == 1),
+                "the range form is built on the EQ form and the shared or the factored one, with one trailing argument");
   __shared__ double lds[SLOT];
   [[maybe_unused]] RgState<RG, 1> rg;
   [[maybe_unused]] const double *blg = nullptr;
   [[maybe_unused]] uint32_t *lowg = nullptr;
   if constexpr (RG) {
-    const RangeArgs ra = [](RangeArgs a) { return a; }(rga...);
+    const auto ra = [](auto a) { return a; }(rga...);
     blg = ra.bl;
     lowg = ra.lower;
   }
   [[maybe_unused]] const double *facg = nullptr;  // FI: the buffer
   [[maybe_unused]] double *faco = nullptr;        // FO: the buffer, and where the finding goes
   [[maybe_unused]] int32_t *fstat = nullptr;
-  if constexpr (FI) facg = [](FactorIn a) { return a; }(rga...).fac;
+  if constexpr (FI) facg = [](auto a) { return a; }(rga...).fac;
   if constexpr (FO) {
     const FactorOut fo = [](FactorOut a) { return a; }(rga...);
     faco = fo.fac;
@@ -350,7 +362,10 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double hi = has_hi ? bv : kInf, lo = has_lo ? rg.lo[0] : -kInf;
     const double beta = __builtin_fmax(has_hi ? __builtin_fabs(hi) : 0.0, has_lo ? __builtin_fabs(lo) : 0.0);
     const bool pre = rowok && has_lo && !has_hi;
-    const double nrm = nrm2 > 0.0 ? nrm2 * rsq(nrm2) : 0.0;
+    // (FI: the stored |a_l| is this very product)
+    double nrm;
+    if constexpr (FI) nrm = nrm2 > 0.0 ? f_an : 0.0;
+    else nrm = nrm2 > 0.0 ? nrm2 * rsq(nrm2) : 0.0;
     rg.low[0] = pre;
     rg.w[0] = (rowok && has_hi && has_lo) ? hi - lo : kInf;
     rg_b = rowok ? (pre ? -lo : hi) : 0.0;
@@ -367,8 +382,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   const double bl = RG ? rg_b : rowok ? bv : 0.0;
   // violated: s / |D row| < -tol (1 + |b| / |D row|), i.e. s < -tol (|D row| + |b|)
   double thr;
-  if constexpr (FI) thr = (rowok && nrm2 > 0.0) ? -feas_tol * (f_an + __builtin_fabs(bl)) : -kInf;
-  else thr = RG ? rg_thr : (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
+  if constexpr (RG) thr = rg_thr;
+  else if constexpr (FI) thr = (rowok && nrm2 > 0.0) ? -feas_tol * (f_an + __builtin_fabs(bl)) : -kInf;
+  else thr = (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
   const bool infeasible0 =
       RG ? rg_inf : wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
   // a row of A with a NaN entry or an overflowing norm fails every comparison
@@ -1083,5 +1099,19 @@ extern "C" hipError_t qpb_launch_gi_wave_factored(const qpb_desc *d, int meq, co
     hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, false, false, qpb::wv::FactorIn>),
                        dim3((unsigned)d->batch), dim3(64), 0, stream, fac, f, fac, b, x, lam, active, status, iters,
                        d->n, d->m, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::FactorIn{fac});
+  return hipGetLastError();
+}
+
+// qpb_solve_range_factored for the n <= 32, m <= 64 class (d->m >= 1): two-sided
+// rows and equality rows 0 .. meq-1 on a factor buffer
+extern "C" hipError_t qpb_launch_gi_wave_range_factored(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                                        const double *bl, const double *bu, double *x, double *lam,
+                                                        uint32_t *active, uint32_t *lower, int32_t *status,
+                                                        int32_t *iters, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, false, qpb::wv::RangeFactorIn>),
+                     dim3((unsigned)d->batch), dim3(64), 0, stream, fac, f, fac, bu, x, lam, active, status, iters,
+                     d->n, d->m | (meq << qpb::wv::kEqShift), (long long)d->batch, max_iter, tol, nullptr,
+                     qpb::wv::RangeFactorIn{fac, bl, lower});
   return hipGetLastError();
 }

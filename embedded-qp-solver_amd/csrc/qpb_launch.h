@@ -70,6 +70,14 @@ typedef hipError_t qpb_gi_factored_launcher(const qpb_desc *d, int meq, const do
                                             int32_t *status, int32_t *iters, hipStream_t stream);
 QPB_LAUNCHER qpb_gi_factored_launcher qpb_launch_gi_factored,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_wave_factored;                               // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_range_factored: the range launchers' rows and outputs on such a
+// buffer; d->m >= 1, d->flags == 0, meq >= 0; either of bl, bu and lower may be NULL
+typedef hipError_t qpb_gi_range_factored_launcher(const qpb_desc *d, int meq, const double *fac, const double *f,
+                                                  const double *bl, const double *bu, double *x, double *lam,
+                                                  uint32_t *active, uint32_t *lower, int32_t *status, int32_t *iters,
+                                                  hipStream_t stream);
+QPB_LAUNCHER qpb_gi_range_factored_launcher qpb_launch_gi_range_factored,  // n <= 16, m <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_range_factored;                                     // n <= 32, m <= 64 (qpb_gi_wave.hip)
 // qpb_solve_shared_backward, pass 1: qpb_launch_kkt_bwd with the same strides
 // (gH / gA NULL where pass 2 sums the gradient)
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long strideH, long long strideA,

@@ -192,6 +192,17 @@ static_assert(route_range(kRangeMaxN, kRangeMaxM).step > 0 && route_range(kRange
 // a range solve's outputs go to qpb_solve_backward unchanged: the same classes
 static_assert(route_range(16, 32).kernel == route_bwd(16, 32).kernel &&
               route_range(32, 64).kernel == route_bwd(32, 64).kernel);
+// qpb_solve_range_factored goes by route_factored (the buffer's layout is the
+// class's): it names route_range's class, and its step, at the classes' corners
+static_assert(route_factored(1, 1).kernel == route_range(1, 1).kernel &&
+              route_factored(16, 32).kernel == route_range(16, 32).kernel &&
+              route_factored(16, 33).kernel == route_range(16, 33).kernel &&
+              route_factored(17, 1).kernel == route_range(17, 1).kernel &&
+              route_factored(32, 64).kernel == route_range(32, 64).kernel);
+static_assert(route_factored(16, 32).step == route_range(16, 32).step &&
+              route_factored(32, 64).step == route_range(32, 64).step && route_factored(33, 1).step == 0 &&
+              route_factored(1, 65).step == 0);
+static_assert(kFactoredMaxN == kRangeMaxN && kFactoredMaxM == kRangeMaxM);
 
 // The slice plan of the batch sum (qpb_kkt_bwd_sum.hip): `slots` consecutive
 // slices of `per` QPs, the last one shorter; one wavefront and one workspace

@@ -102,6 +102,10 @@ _lib.qpb_solve_range.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_
 _lib.qpb_solve_range.restype = ctypes.c_int
 _lib.qpb_solve_range_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_range_host.restype = ctypes.c_int
+_lib.qpb_solve_range_factored.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
+_lib.qpb_solve_range_factored.restype = ctypes.c_int
+_lib.qpb_solve_range_factored_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
+_lib.qpb_solve_range_factored_host.restype = ctypes.c_int
 _lib.qpb_solve_box.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box.restype = ctypes.c_int
 _lib.qpb_solve_box_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
@@ -635,6 +639,75 @@ def solve_range_host(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_t
                                    p(bl) if m else None, p(bu) if m else None, p(x), p(lam), p(act), p(low), p(st),
                                    p(it))
     _check(rc, "qpb_solve_range_host")
+    return RangeSolution(x, lam, act, low, st, it)
+
+
+def solve_range_factored(F: SharedFactor, f, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                         out: RangeSolution | None = None, stream=None) -> RangeSolution:
+    """``solve_range`` with a 2-D H and A, without the per-QP set-up
+    (qpb_solve_range_factored): ``F`` is ``factor_shared(H, A)`` -- the buffer
+    ``solve_factored`` takes, unchanged -- and f (B, n), bl and bu (B, m) are per
+    QP; ``bl`` or ``bu`` may be None.  The contract is ``solve_range``'s except
+    that x and lam may differ from it by rounding and ``iters`` need not be the
+    same.  An MPC loop factors once per model and calls this every tick."""
+    import torch
+    if not (f.is_cuda and F.fac.is_cuda):
+        raise ValueError("qpb.solve_range_factored expects CUDA (HIP) tensors; use solve_range_factored_host for numpy")
+    n, m = int(F.n), int(F.m)
+    if m and bl is None and bu is None:
+        raise ValueError("qpb.solve_range_factored needs at least one of bl and bu")
+    if f.dtype != torch.float64 or not f.is_contiguous() or f.device != F.fac.device:
+        raise ValueError("f must be a contiguous float64 tensor on the factor's CUDA device")
+    if f.dim() != 2 or f.shape[1] != n:
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    B = f.shape[0]
+    for t in (bl, bu):
+        if m and t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != f.device
+                                    or tuple(t.shape) != (B, m)):
+            raise ValueError(f"bl and bu must be contiguous float64 (B, m) tensors on the factor's device: the "
+                             f"factor is for n={n}, m={m}")
+        if not m and t is not None and t.numel():
+            raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    if F.fac.dtype != torch.float64 or tuple(F.fac.shape) != (factor_doubles(n, m),) or not F.fac.is_contiguous():
+        raise ValueError(f"the factor buffer is not one for n={n}, m={m}")
+    if out is None:
+        out = _empty_range_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_range_factored(ctypes.byref(d), int(meq), _ptr(F.fac), _ptr(f),
+                                       _ptr(bl) if m and bl is not None else None,
+                                       _ptr(bu) if m and bu is not None else None, _ptr(out.x), _ptr(out.lam),
+                                       _ptr(out.active), _ptr(out.lower), _ptr(out.status), _ptr(out.iters),
+                                       _stream_ptr(stream))
+    _check(rc, "qpb_solve_range_factored")
+    return out
+
+
+def solve_range_factored_host(F: SharedFactor, f, bl, bu, meq: int = 0, *, max_iter: int = 0,
+                              feas_tol: float = 0.0) -> RangeSolution:
+    """numpy in / numpy out (qpb_solve_range_factored_host): ``solve_range_factored`` with host arrays."""
+    import numpy as np
+    n, m = int(F.n), int(F.m)
+    fac = np.ascontiguousarray(F.fac, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if m:
+        bl = None if bl is None else np.ascontiguousarray(bl, dtype=np.float64)
+        bu = None if bu is None else np.ascontiguousarray(bu, dtype=np.float64)
+    B = f.shape[0]
+    if f.shape != (B, n) or fac.shape != (factor_doubles(n, m),) or (
+            m and any(t is not None and t.shape != (B, m) for t in (bl, bu))):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    w = (m + 31) // 32
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, w), dtype=np.uint32)
+    low = np.zeros((B, w), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_range_factored_host(ctypes.byref(d), int(meq), p(fac), p(f), p(bl) if m else None,
+                                            p(bu) if m else None, p(x), p(lam), p(act), p(low), p(st), p(it))
+    _check(rc, "qpb_solve_range_factored_host")
     return RangeSolution(x, lam, act, low, st, it)
 
 

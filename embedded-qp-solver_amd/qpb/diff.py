@@ -24,7 +24,8 @@ and ub (``qpb.solve_box_backward``, n <= 32).
 ``solve_range(H, f, A, bl, bu, meq)`` is ``qpb.solve_range`` with gradients for
 H, f, A, bl and bu: the backward is ``qpb.solve_backward`` (or the shared one)
 on the range solve's outputs, its ``gb`` routed to ``bl`` or ``bu`` by the
-``lower`` bits.
+``lower`` bits.  ``prefactor=True`` (a 2-D H and a 2-D A) factors once per
+forward and solves with ``qpb.solve_range_factored``; the backward is unchanged.
 """
 from __future__ import annotations
 
@@ -98,12 +99,16 @@ class RangeQPFunction(torch.autograd.Function):
     """x*(H, f, A, bl, bu) of min 1/2 x'Hx + f'x s.t. A[:meq] x = bu[:meq], bl[meq:] <= A[meq:] x <= bu[meq:]."""
 
     @staticmethod
-    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol):
+    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol, prefactor):
         H, f, A = H.contiguous(), f.contiguous(), A.contiguous()
         bl = None if bl is None else bl.contiguous()
         bu = None if bu is None else bu.contiguous()
         # above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
-        sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
+        if prefactor:
+            sol = qpb.solve_range_factored(qpb.factor_shared(H, A), f, bl, bu, meq, max_iter=max_iter,
+                                           feas_tol=feas_tol)
+        else:
+            sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
         ctx.shared = H.dim() == 2 or A.dim() == 2
         ctx.meq = meq
         ctx.has = (True, True, True, bl is not None, bu is not None)
@@ -117,7 +122,7 @@ class RangeQPFunction(torch.autograd.Function):
         want = [w and has for w, has in zip(ctx.needs_input_grad[:5], ctx.has)]
         wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if want[3] or want[4] else [])
         if not wanted:
-            return (None,) * 8
+            return (None,) * 9
         sol = qpb.Solution(x, lam, active, status, None)
         backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
         gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
@@ -133,10 +138,11 @@ class RangeQPFunction(torch.autograd.Function):
                 gbl = torch.where(low, gb, zero)
             if want[4]:
                 gbu = torch.where(low, zero, gb)
-        return gH, gf, gA, gbl, gbu, None, None, None
+        return gH, gf, gA, gbl, gbu, None, None, None, None
 
 
-def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                prefactor: bool = False):
     """Differentiable batched solve with two-sided rows (``qpb.solve_range`` with
     gradients): returns ``(x, status)``; ``x`` carries gradients to whichever of
     H, f, A, bl and bu require them.  The backward is ``qpb.solve_backward`` (with
@@ -144,8 +150,16 @@ def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: f
     active and status; its ``gb`` goes to ``bu`` on the rows < meq and on the
     rows active at their upper bound, to ``bl`` on the rows whose ``lower`` bit
     is set.  A bound passed as None gets no gradient.  n <= 32 and m <= 64: above
-    that the forward raises ``QPBError(ERR_UNSUPPORTED)``."""
-    return RangeQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol))
+    that the forward raises ``QPBError(ERR_UNSUPPORTED)``.  ``prefactor=True``
+    needs a 2-D H and a 2-D A, else ValueError: the forward factors them once
+    (``qpb.factor_shared``) and solves with ``qpb.solve_range_factored``, whose
+    x may differ from the default's by rounding; the backward is the same
+    ``qpb.solve_shared_backward`` on H and A.  The default is today's call, bit
+    for bit."""
+    if prefactor:
+        if H.dim() != 2 or A.dim() != 2:
+            raise ValueError("prefactor=True needs a 2-D H (n, n) and a 2-D A (m, n): one matrix for the batch")
+    return RangeQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol), bool(prefactor))
 
 
 def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0):

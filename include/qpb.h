@@ -17,6 +17,7 @@
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
  *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
+ *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -395,8 +396,8 @@ int qpb_factor_shared_host(int32_t n, int32_t m, const double *H,
  * missing pointers QPB_ERR_INVALID_ARG (fac, f, x and status always; b, lam and
  * active with m > 0; iters may be NULL); a missing device last.
  * Follow-ups: a factored qpb_solve_shared_backward (kkt_bwd re-factors H and
- * re-forms A_W L^-T per QP), a factored range form, and a shared H with a
- * per-QP A.
+ * re-forms A_W L^-T per QP) and a shared H with a per-QP A.  Two-sided rows on
+ * the same buffer: qpb_solve_range_factored, below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_factored(const qpb_desc *desc, int32_t meq, const double *fac,
 		       const double *f, const double *b, double *x, double *lam,
@@ -525,7 +526,8 @@ int qpb_solve_shared_backward_host(const qpb_desc *desc, int32_t shared,
  * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
  * with m <= 64.  Follow-ups: the n <= 128 Gram class, QPB_FLAG_MIXED,
  * qpb_solve_sections and a range form of qpb_solve_box (general rows beside a
- * box) have no range form.
+ * box) have no range form.  With one H and A for every call of a loop, the
+ * set-up need not be repeated per QP: qpb_solve_range_factored, below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_range(const qpb_desc *desc, int32_t meq, int32_t shared,
 		    const double *H, const double *f, const double *A,
@@ -539,6 +541,54 @@ int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
 			 const double *bl, const double *bu, double *x,
 			 double *lam, uint32_t *active, uint32_t *lower,
 			 int32_t *status, int32_t *iters);
+
+/* qpb_solve_range(shared = QPB_SHARED_H | QPB_SHARED_A) without the per-QP
+ * set-up: two-sided rows on a buffer of qpb_factor_shared for (desc->n,
+ * desc->m) -- the buffer qpb_solve_factored takes, unchanged, so one buffer
+ * serves both calls, in any order and at once.  This is the MPC call: the plant
+ * model H and A is factored once, the state and rate limits are two-sided
+ * rows, and every tick solves with its own f, bl and bu.
+ * The contract is qpb_solve_range's on the H and A the buffer was made from,
+ * every sentence of it: the signed lam, `active` as the backward reads it,
+ * `lower` (may be NULL), NaN and +-inf bounds as absent sides, bl or bu NULL,
+ * one threshold per row with the larger finite |bound|, crossed bounds and a
+ * zero row of A judged against each QP's own bl and bu, zero width, the
+ * equality rows' rules, and what is written at every status; a QP's outputs
+ * depend on its own f, bl and bu and on fac only.  The thresholds are the
+ * unfactored call's bit for bit: they are formed from the |a_r| the buffer
+ * stores.  Two things differ, the two that qpb_solve_factored has against
+ * qpb_solve_shared: x and lam may differ by rounding (s = b + D y is formed from
+ * the stored L and D; a row whose only bound is the lower one takes the negated
+ * stored row of D), and iters may differ.  On a non-degenerate QP status,
+ * active and lower are the same.
+ * A buffer whose H was not SPD gives every QP QPB_NOT_SPD, one with a NaN row
+ * of A gives every QP QPB_NUMERICAL; in both cases iters = 0, lam = 0,
+ * active = 0 and lower = 0.  The buffer is only read.
+ *   m == 0   the call is qpb_solve_factored, its outputs bit for bit; `lower`
+ *            has no words and is not written.
+ * Errors, in order: the descriptor as qpb_solve; meq < 0 or desc->flags != 0
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64 QPB_ERR_UNSUPPORTED; meq > m
+ * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
+ * missing pointers QPB_ERR_INVALID_ARG (fac, f, x and status always; with m > 0
+ * lam, active and at least one of bl and bu; lower and iters may be NULL); a fac
+ * that is not 16-byte aligned QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits as qpb_solve_factored.  Follow-ups: a factored
+ * qpb_solve_shared_backward for the same buffer (the backward of this call is
+ * qpb_solve_shared_backward on H and A, unchanged), and the Gram class.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_range_factored(const qpb_desc *desc, int32_t meq,
+			     const double *fac, const double *f,
+			     const double *bl, const double *bu, double *x,
+			     double *lam, uint32_t *active, uint32_t *lower,
+			     int32_t *status, int32_t *iters, void *stream);
+
+/* Same with host pointers (fac included: the call uploads it). */
+int qpb_solve_range_factored_host(const qpb_desc *desc, int32_t meq,
+				  const double *fac, const double *f,
+				  const double *bl, const double *bu, double *x,
+				  double *lam, uint32_t *active,
+				  uint32_t *lower, int32_t *status,
+				  int32_t *iters);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
