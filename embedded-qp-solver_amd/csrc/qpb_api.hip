@@ -671,6 +671,169 @@ extern "C" int qpb_solve_factored_host(const qpb_desc *d, int32_t meq, const dou
   return 0;
 }
 
+// ---- the backward on a buffer of its own ----------------------------------------
+extern "C" int64_t qpb_factor_backward_doubles(int32_t n, int32_t m) {
+  if (n < 1 || m < 0) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_backward_doubles: n must be >= 1 and m >= 0");
+  if (qpb::route_factored_bwd(n, m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_factor_backward_doubles: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", n, m,
+                qpb::kFactoredBwdMaxN, qpb::kFactoredBwdMaxM);
+  return qpb::bfct::layout(n, m).size;
+}
+
+// the rules of qpb_factor_shared_backward up to the device: check_factor's
+static int check_factor_bwd(int32_t n, int32_t m, const double *H, const double *A, const double *bfac) {
+  if (n < 1 || m < 0) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_shared_backward: n must be >= 1 and m >= 0");
+  if (qpb::route_factored_bwd(n, m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_factor_shared_backward: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", n, m,
+                qpb::kFactoredBwdMaxN, qpb::kFactoredBwdMaxM);
+  if (!H || !bfac) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_shared_backward: H and bfac are required");
+  if (m > 0 && !A) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_shared_backward: A is required when m > 0");
+  return 0;
+}
+
+extern "C" int qpb_factor_shared_backward(int32_t n, int32_t m, const double *H, const double *A, double *bfac,
+                                          int32_t *fstatus, void *stream) {
+  int rc = check_factor_bwd(n, m, H, A, bfac);
+  if (rc) return rc;
+  if ((uintptr_t)bfac & 15)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_factor_shared_backward: bfac must be 16-byte aligned");
+  rc = check_device();
+  if (rc) return rc;
+  const hipError_t e = qpb_launch_kkt_bwd_factor(n, m, H, m > 0 ? A : nullptr, bfac, fstatus, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(e, "qpb_factor_shared_backward launch");
+}
+
+// qpb_solve_factored_backward's argument rules after check_desc, up to batch == 0
+static int check_factored_bwd(const qpb_desc *d) {
+  if (d->flags != 0)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: flags must be 0 (got %d)", d->flags);
+  if (qpb::route_factored_bwd(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_solve_factored_backward: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", d->n,
+                d->m, qpb::kFactoredBwdMaxN, qpb::kFactoredBwdMaxM);
+  return 0;
+}
+static int check_factored_bwd_arrays(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
+                                     const uint32_t *active, const double *gx, const double *gH, const double *gf,
+                                     const double *gA, const double *gb) {
+  if (!bfac || !x || !gx) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: bfac, x and gx are required");
+  if (d->m > 0 && (!lam || !active))
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: lam and active are required when m > 0");
+  if (!gH && !gf && !(d->m > 0 && (gA || gb)))
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: at least one of gH, gf, gA and gb is required");
+  return 0;
+}
+
+// qpb_solve_shared_backward's body with both operands shared and the factored
+// pass 1: the same chunk walk, workspace and pass 2
+extern "C" int qpb_solve_factored_backward(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
+                                           const uint32_t *active, const int32_t *status, const double *gx,
+                                           double *gH, double *gf, double *gA, double *gb, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_factored_bwd(d);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb);
+  if (rc) return rc;
+  if ((uintptr_t)bfac & 15)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: bfac must be 16-byte aligned");
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_factored_bwd(d->n, d->m);
+  const long long n = d->n, m = d->m, B = d->batch;
+  if (m == 0) gA = gb = nullptr;  // ignored
+  const hipStream_t st = (hipStream_t)stream;
+  // pass 1 over the batch in chunks (the buffer's QP stride is 0); gf1 and gb1
+  // are the caller's, or the workspace's where pass 2 needs them
+  auto pass1 = [&](double *gf1, double *gb1) {
+    return qpb::for_each_chunk(
+        B, r.step,
+        [&](long long count, const double *Fc, const double *xc, const double *lc, const uint32_t *ac,
+            const int32_t *sc, const double *gxc, double *gfc, double *gbc) {
+          qpb_desc c = *d;
+          c.batch = count;
+          const hipError_t e = qpb_launch_kkt_bwd_factored(&c, Fc, xc, lc, ac, sc, gxc, gfc, gbc, st);
+          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_factored_backward launch");
+        },
+        qpb::required(bfac, 0), qpb::required(x, n), qpb::optional(lam, m), qpb::optional(active, (m + 31) / 32),
+        qpb::optional(status, 1), qpb::required(gx, n), qpb::optional(gf1, n), qpb::optional(gb1, m));
+  };
+  if (!gH && !gA) return pass1(gf, gb);  // the summed gradients are not wanted: pass 1 alone
+  // workspace, as qpb_solve_shared_backward's: the slots, then dx (B n) where gf
+  // is not given, then gb (B m) where gA is summed and gb is not given
+  const long long slot_doubles = qpb::sum_plan(B).slots * qpb::sum_slot_doubles(d->n, d->m);
+  const long long ws_dx = gf ? 0 : B * n, ws_gb = (gA && !gb) ? B * m : 0;
+  const hipError_t e = qpb_with_workspace(st, (size_t)(slot_doubles + ws_dx + ws_gb) * 8, [&](void *ws) {
+    double *const slots = (double *)ws;
+    double *const dx = gf ? gf : slots + slot_doubles;
+    double *const gbs = gb ? gb : gA ? slots + slot_doubles + ws_dx : nullptr;
+    rc = pass1(dx, gbs);
+    if (rc) return hipSuccess;  // reported through rc
+    return qpb_launch_kkt_bwd_sum(d, x, dx, gbs, lam, active, status, slots, gH, gA, st);
+  });
+  if (rc) return rc;
+  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_factored_backward sum launch");
+}
+
+extern "C" int qpb_factor_shared_backward_host(int32_t n, int32_t m, const double *H, const double *A, double *bfac,
+                                               int32_t *fstatus) {
+  int rc = check_factor_bwd(n, m, H, A, bfac);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t N = n, M = m, doubles = (size_t)qpb::bfct::layout(n, m).size;
+  DevBuf dH, dA, dF, dS;
+  HIPCHK(up(dH, H, N * N * 8), "H");
+  HIPCHK(up(dA, M ? A : nullptr, M * N * 8), "A");
+  HIPCHK(alloc(dF, bfac, doubles * 8), "bfac");
+  HIPCHK(alloc(dS, fstatus, 4), "fstatus");
+  rc = qpb_factor_shared_backward(n, m, (double *)dH.p, (double *)dA.p, (double *)dF.p, (int32_t *)dS.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_factor_shared_backward_host kernel");
+  HIPCHK(down(bfac, dF, doubles * 8), "bfac D2H");
+  HIPCHK(down(fstatus, dS, 4), "fstatus D2H");
+  return 0;
+}
+
+extern "C" int qpb_solve_factored_backward_host(const qpb_desc *d, const double *bfac, const double *x,
+                                                const double *lam, const uint32_t *active, const int32_t *status,
+                                                const double *gx, double *gH, double *gf, double *gA, double *gb) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_factored_bwd(d);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
+  DevBuf dF, dx, dl, da, ds, dg, oH, of, oA, ob;
+  HIPCHK(up(dF, bfac, (size_t)qpb::bfct::layout(d->n, d->m).size * 8), "bfac");
+  HIPCHK(up(dx, x, B * n * 8), "x");
+  HIPCHK(up(dl, m ? lam : nullptr, B * m * 8), "lam");
+  HIPCHK(up(da, m ? active : nullptr, B * w * 4), "active");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(alloc(oH, gH, n * n * 8), "gH");
+  HIPCHK(alloc(of, gf, B * n * 8), "gf");
+  HIPCHK(alloc(oA, m ? gA : nullptr, m * n * 8), "gA");
+  HIPCHK(alloc(ob, m ? gb : nullptr, B * m * 8), "gb");
+  rc = qpb_solve_factored_backward(d, (double *)dF.p, (double *)dx.p, (double *)dl.p, (uint32_t *)da.p,
+                                   (int32_t *)ds.p, (double *)dg.p, (double *)oH.p, (double *)of.p, (double *)oA.p,
+                                   (double *)ob.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_factored_backward_host kernel");
+  HIPCHK(down(gH, oH, n * n * 8), "gH D2H");
+  HIPCHK(down(gf, of, B * n * 8), "gf D2H");
+  HIPCHK(down(m ? gA : nullptr, oA, m * n * 8), "gA D2H");
+  HIPCHK(down(m ? gb : nullptr, ob, B * m * 8), "gb D2H");
+  return 0;
+}
+
 // ---- two-sided rows bl <= A x <= bu -------------------------------------------
 // qpb_solve_range's argument rules after check_desc, up to batch == 0
 static int check_range(const qpb_desc *d, int32_t meq, int32_t shared) {
@@ -1104,4 +1267,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed; kkt_bwd_fact v1.0: qpb_solve_factored_backward for n <= 32 and m <= 64, a shared H and A factored once by the backward kernels' own set-up into a buffer of the backward's own that holds L, 1 / L_kk, D = A L^-T and the sweep's multipliers, the factored forms of kkt_bwd take u from them by the set-up's own operations, outputs bit for bit those of qpb_solve_shared_backward)"; }

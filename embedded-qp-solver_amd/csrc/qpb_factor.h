@@ -73,4 +73,68 @@ static_assert(layout(16, 32).D % 2 == 0 && layout(16, 32).L % 2 == 0 && layout(3
               layout(7, 5).D % 2 == 0 && layout(20, 3).D % 2 == 0);
 
 }  // namespace fct
+
+// The backward's buffer (qpb_factor_shared_backward -> qpb_solve_factored_backward),
+// a layout of its own: it is written by the backward kernels' own set-up
+// (qpb_kkt_bwd.hip), so that what remains per QP is the unfactored kernel's
+// operations on the unfactored kernel's numbers, and it holds neither A nor the
+// row norms -- no output of the backward reads them.  One (n, m), one class,
+// offsets in doubles, as above.
+//
+//   header (kHdr)   [0] 0 or QPB_NOT_SPD (a pivot that was not a positive finite
+//                   number), as a double; [1] n; [2] m; [3] 16 or 32
+//   n <= 16, m <= 32 (kkt_bwd_dense_kernel: lane l of a QP's 16 holds row l of L
+//   and rows l + 16 r of D, r < MR):
+//     L    the packed lower triangle as store_l leaves it in the LDS slot, 136
+//          doubles, zero up to kDenseL: 16-byte piece t 16 + l by lane l, t < 5
+//     ik   [k]: 1 / L_kk, the sweep's ik of step k = the kernel's invLd of lane k
+//     nc   [t][l][c], t < 8, c < 2: the multiplier nc of lane l at step 2t + c of
+//          the u recursion
+//     D    [r][t][l][c]: the lane's E[r][2t + c] after the sweep; rows >= m and
+//          columns >= n zero
+//   otherwise, n <= 32, m <= 64 (kkt_bwd_wave_kernel: lane j < 32 holds component j):
+//     L    the kernel's 32 x 33 LDS image after the factorisation, padding
+//          included (the rows' 33rd words zero): a flat copy
+//     ik   [j]: 1 / L_jj, 1 on the padding (the kernel's invLd of lane j)
+//     D    [r][j], r < m: row r of A L^-T by the kernel's forward substitution
+namespace bfct {
+
+constexpr int kHdr = fct::kHdr;
+constexpr int kMaxN = fct::kMaxN, kMaxM = fct::kMaxM;
+constexpr int kDenseL = 160;           // 136 rounded up to a 16-byte piece per lane and load
+constexpr int kWaveL = 32 * 33;        // WN * WS of qpb_kkt_bwd.hip
+
+struct Layout {
+  bool dense;  // the n <= 16, m <= 32 class
+  int mr;      // dense: rows of D per lane
+  long long L, ik, nc, D;  // offsets (nc: dense only)
+  long long size;          // doubles in all
+};
+
+constexpr Layout layout(int n, int m) {
+  Layout y{};
+  y.dense = n <= 16 && m <= 32;
+  y.mr = m <= 16 ? 1 : 2;
+  y.L = kHdr;
+  y.ik = y.L + (y.dense ? kDenseL : kWaveL);
+  y.nc = y.ik + (y.dense ? 16 : 32);
+  y.D = y.nc + (y.dense ? 256 : 0);
+  y.size = y.D + (y.dense ? 256LL * y.mr : 32LL * m);
+  return y;
+}
+
+static_assert(layout(16, 32).dense && layout(16, 32).mr == 2 && !layout(16, 33).dense && !layout(17, 0).dense);
+static_assert(layout(16, 32).dense == fct::layout(16, 32).dense && layout(16, 33).dense == fct::layout(16, 33).dense &&
+              layout(17, 0).dense == fct::layout(17, 0).dense);
+static_assert(layout(16, 32).size == 8 + 160 + 16 + 256 + 512 && layout(1, 0).size == 8 + 160 + 16 + 256 + 256);
+static_assert(layout(32, 64).size == 8 + 1056 + 32 + 2048 && layout(17, 0).size == 8 + 1056 + 32 &&
+              layout(16, 33).size == 8 + 1056 + 32 + 33 * 32);
+// every section starts on a 16-byte boundary (the b128 loads and copies)
+static_assert(layout(16, 32).L % 2 == 0 && layout(16, 32).ik % 2 == 0 && layout(16, 32).nc % 2 == 0 &&
+              layout(16, 32).D % 2 == 0 && layout(7, 5).D % 2 == 0 && layout(7, 5).size % 2 == 0);
+static_assert(layout(32, 64).L % 2 == 0 && layout(32, 64).ik % 2 == 0 && layout(32, 64).D % 2 == 0 &&
+              layout(20, 3).D % 2 == 0 && layout(20, 3).size % 2 == 0);
+static_assert(kDenseL % 32 == 0 && kDenseL >= 16 * 17 / 2 && kWaveL % 2 == 0);
+
+}  // namespace bfct
 }  // namespace qpb

@@ -39,6 +39,7 @@
 // column t goes to LDS in the slot's layout (column-major, zero diagonal,
 // 1 / R_tt in lane t), so both triangular solves are the lane-parallel
 // DPP-fused back substitution (row16::back_subst_step).
+#include "qpb_factor.h"  // the backward's buffer
 #include "qpb_launch.h"  // with qpb.h
 #include "qpb_row16.h"
 
@@ -61,6 +62,26 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
   return p + q;
 }
 
+// What a form reads of a QP before its set-up.  The factor form (FM == 1) has
+// no QP: nothing is loaded.  On a buffer (FM == 2, `fac`) whose H was not
+// positive definite no QP counts as QPB_OK.
+template <int FM>
+__device__ __forceinline__ bool form_ok(const int32_t *statg, long long g, const double *fac) {
+  if constexpr (FM == 1) return true;
+  else if constexpr (FM == 2) return (statg ? statg[g] == QPB_OK : true) && fac[0] != (double)QPB_NOT_SPD;
+  else return statg ? statg[g] == QPB_OK : true;
+}
+template <int FM>
+__device__ __forceinline__ uint32_t form_mask(const uint32_t *actg, long long g) {
+  if constexpr (FM == 1) return 0u;
+  else return actg[g];
+}
+template <int FM>
+__device__ __forceinline__ double form_gx(const double *gxg, long long e) {
+  if constexpr (FM == 1) return 0.0;
+  else return gxg[e];
+}
+
 // MR: rows of A per lane (m <= 16 MR).  N16: n == 16 (coalesced loads and
 // stores through this QP's LDS slot); otherwise the rows are padded with the
 // identity and padded variables take no part.
@@ -68,12 +89,23 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
 // whole batch, its QP stride 0; the QPB_SHARED_* bits ride in `m`, at kShShift.
 constexpr int kShShift = 28;
 static_assert(QPB_MAX_M < (1 << kShShift) && (3 << kShShift) > 0);
-template <int MR, bool N16, bool SH = false>
+// FMP (empty, or Form<FM>): the forms around a backward factor buffer
+// (qpb_factor.h, bfct).  FM == 1, qpb_factor_shared_backward's kernel: one
+// workgroup runs this form's own load and sweep on the one H (Hg) and A (Ag)
+// and its first row writes the buffer (gHg; the finding also to the int32 at
+// gbg, which may be NULL) -- no QP is read.  FM == 2, qpb_solve_factored_backward:
+// Hg is the buffer; L, 1 / L_kk, D and the multipliers of the u recursion are
+// loaded and no sweep runs.  From the orthogonalisation on the code is one.
+template <int FM>
+using Form = std::integral_constant<int, FM>;
+template <int MR, bool N16, bool SH = false, class... FMP>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
     const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
     double *__restrict__ gbg, int n, int m, long long batch) {
+  constexpr int FM = (0 + ... + FMP::value);
+  static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   __shared__ double lds[QPB * SLOT];
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -96,13 +128,58 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   // m == 0: the (masked) row loads read H
   const double *Aq =
       m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n) : Hq;
-  const bool ok = statg ? statg[g] == QPB_OK : true;
+  // (FM == 2: nor does any QP on a buffer whose H was not positive definite)
+  const bool ok = form_ok<FM>(statg, g, Hg);
   // a QP that is not QPB_OK takes no trips and stores zeros
-  uint32_t W = (m > 0 && ok) ? actg[g] : 0u;
+  uint32_t W = (m > 0 && ok) ? form_mask<FM>(actg, g) : 0u;
   if (m < 32) W &= (1u << m) - 1u;
-  const double gv = gxg[g * n + lc];
+  const double gv = form_gx<FM>(gxg, g * n + lc);
   double Lr[NL];     // row l of H, becomes row l of L
   double E[MR][NL];  // rows l, l + 16 of A, become rows of D = A L^{-T}
+  double ya, ul, invLd;
+  if constexpr (FM == 2) {
+    ya = var ? gv : 0.0, ul = 0.0;
+    // The buffer in place of H and A: every load is 16 bytes per lane at
+    // consecutive addresses over the QP's lanes, the same for the wave's four
+    // QPs.  L goes straight to the slot.
+    constexpr bfct::Layout y = bfct::layout(NL, NL * MR);
+    const double *fac = Hg;
+#pragma unroll
+    for (int t = 0; t < bfct::kDenseL / (2 * NL); ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&fac[y.L + (t * NL + l) * 2]);
+      if ((t * NL + l) * 2 < L_SIZE) *reinterpret_cast<double2 *>(&Lp[(t * NL + l) * 2]) = v;
+    }
+    invLd = fac[y.ik + l];
+    double nc[NL];
+#pragma unroll
+    for (int t = 0; t < NL / 2; ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&fac[y.nc + (t * NL + l) * 2]);
+      nc[2 * t] = v.x;
+      nc[2 * t + 1] = v.y;
+    }
+    // u = L^{-1} g from the sweep's multipliers in the sweep's order and with
+    // its instruction: u_k = g_k / L_kk is taken on lane k at step k (there
+    // the lane's own 1 / L_ll is the step's), then g += g_k nc_k.  The FMA
+    // reads the g it wrote the step before: the hazard's wait states each time.
+    unroll<NL>([&](auto K) {
+      constexpr int k = K;
+      ul = l == k ? ya * invLd : ul;
+      pin(ul);  // (as in the sweep: the select would sink with every step's g alive)
+      fmac_bc_nop<k>(ya, ya, nc[k]);
+    });
+    // (D after u: the multipliers are dead by then, and nothing may hoist the
+    // loads above it -- the 32 registers of nc beside the 64 of D spill)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < MR; ++r)
+#pragma unroll
+      for (int t = 0; t < NL / 2; ++t) {
+        const double2 v = *reinterpret_cast<const double2 *>(&fac[y.D + ((r * (NL / 2) + t) * NL + l) * 2]);
+        E[r][2 * t] = v.x;
+        E[r][2 * t + 1] = v.y;
+      }
+    wave_lds_sync();
+  } else {  // (the unfactored load and sweep keep their indentation, down to "FM != 2")
   if constexpr (N16) {
     // coalesced 16-byte loads, two whole rows of each of the wave's 4 QPs per
     // instruction; the rows reach their owner lanes through a transpose in
@@ -161,7 +238,8 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   // trailing block agree to eps |H| only, which next to a pivot of 1e-10 |H| is
   // another L -- and D from one L with u and dx from the other broke both
   // certificates at cond(H) = 1e10 (1e-9 where the wave kernel has 1e-15).
-  double ya = var ? gv : 0.0, ul = 0.0, invLd = 0.0;
+  ya = var ? gv : 0.0, ul = 0.0, invLd = 0.0;
+  [[maybe_unused]] bool spd = true;               // FM == 1: every pivot was a positive finite number
   unroll<NL>([&](auto K) {
     constexpr int k = K;
     __builtin_amdgcn_sched_barrier(0);
@@ -169,6 +247,11 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double ik = rsq1(akk);
     const double ik2 = ik * ik;
     const double nc = -(Lr[k] * ik2);
+    if constexpr (FM == 1) {
+      // the lane's multiplier of the step, to its place in the buffer
+      if (slot == 0) gHg[bfct::layout(NL, NL * MR).nc + ((k / 2) * NL + l) * 2 + (k & 1)] = nc;
+      spd = spd && akk > 0.0 && akk < kInf;
+    }
     double ne2[MR];
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
@@ -194,6 +277,33 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   });
   __builtin_amdgcn_sched_barrier(0);
   store_l(Lp, l, Lr);  // for the last solve
+  if constexpr (FM == 1) {
+    // ---- the factor kernel ends here: the first row writes the buffer, L as
+    // the slot holds it
+    wave_lds_sync();
+    if (slot == 0) {
+      constexpr bfct::Layout y = bfct::layout(NL, NL * MR);
+      double *fac = gHg;
+      const int found = spd ? QPB_OK : QPB_NOT_SPD;
+      if (l < bfct::kHdr) fac[l] = l == 0 ? (double)found : l == 1 ? (double)n : l == 2 ? (double)m : l == 3 ? 16.0 : 0.0;
+      if (l == 0 && gbg) *reinterpret_cast<int32_t *>(gbg) = found;
+#pragma unroll
+      for (int t = 0; t < bfct::kDenseL / (2 * NL); ++t) {
+        const int e = (t * NL + l) * 2;
+        *reinterpret_cast<double2 *>(&fac[y.L + e]) =
+            e < L_SIZE ? *reinterpret_cast<const double2 *>(&Lp[e]) : make_double2(0.0, 0.0);
+      }
+      fac[y.ik + l] = invLd;
+#pragma unroll
+      for (int r = 0; r < MR; ++r)
+#pragma unroll
+        for (int t = 0; t < NL / 2; ++t)
+          *reinterpret_cast<double2 *>(&fac[y.D + ((r * (NL / 2) + t) * NL + l) * 2]) =
+              make_double2(E[r][2 * t], E[r][2 * t + 1]);
+    }
+    return;
+  }
+  }  // FM != 2
   // R zeroed in pairs at lane-rotated positions (qpb_gi_box.hip)
 #pragma unroll
   for (int j = 0; j < NL; j += 2)
@@ -417,12 +527,20 @@ __device__ __forceinline__ double wave_sum(double t) {
   return (readlane_d(t, 0) + readlane_d(t, 16)) + (readlane_d(t, 32) + readlane_d(t, 48));
 }
 
-template <bool SH = false>
+// FMP: the dense kernel's forms around a backward factor buffer.  FM == 1 runs
+// the factorisation on the one H and the forward substitution for all m rows
+// of the one A, and writes the buffer (gHg, the finding also to the int32 at
+// gbg); FM == 2 (Hg is the buffer) copies L's image into LDS, takes u from the
+// stored L and 1 / L_kk by the operations of the factorisation loop, and an
+// active row's v is one load.
+template <bool SH = false, class... FMP>
 __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
     const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
     double *__restrict__ gbg, int n, int m, long long batch) {
+  constexpr int FM = (0 + ... + FMP::value);
+  static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -440,17 +558,28 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   double *vb = lds + W_V, *cb = lds + W_C, *ub = lds + W_U, *ir = lds + W_IR, *posb = lds + W_POS;
   const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
   const double *Aq = SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n;
-  const bool ok = statg ? statg[g] == QPB_OK : true;
+  const bool ok = form_ok<FM>(statg, g, Hg);
   // the active mask as one 64-bit word (wave-uniform); a QP that is not QPB_OK takes no trips
   const int words = (m + 31) / 32;
   unsigned long long W = 0;
-  if (ok && m > 0) {
+  if (FM != 1 && ok && m > 0) {
     W = actg[g * words];
     if (words > 1) W |= (unsigned long long)actg[g * words + 1] << 32;
     if (m < 64) W &= (1ull << m) - 1ull;
   }
   W = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(W >> 32)) << 32) |
       (unsigned)__builtin_amdgcn_readfirstlane((int)W);
+  [[maybe_unused]] const bfct::Layout fy = bfct::layout(FM != 0 ? n : 17, m);  // the wave class's offsets
+  if constexpr (FM == 2) {
+    // L's image as the factor kernel left it, Q zero
+    static_assert(W_L == 0 && bfct::kWaveL == WN * WS && bfct::kWaveL % 2 == 0);
+    for (int e = lane; e < bfct::kWaveL / 2; e += 64) {
+      const double2 v = *reinterpret_cast<const double2 *>(&Hg[fy.L + 2 * e]);
+      Lm[2 * e] = v.x;
+      Lm[2 * e + 1] = v.y;
+    }
+    for (int e = lane; e < WN * WN; e += 64) Qm[(e >> 5) * WS + (e & (WN - 1))] = 0.0;
+  } else {  // (the unfactored load keeps its indentation)
   // H padded with the identity, Q zero
   for (int e = lane; e < WN * WN; e += 64) {
     const int row = e >> 5, col = e & (WN - 1);
@@ -459,19 +588,35 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     Lm[row * WS + col] = in ? h : (row == col ? 1.0 : 0.0);
     Qm[row * WS + col] = 0.0;
   }
+  }
   posb[lane] = -1.0;
   if (lane < W_COL) colk[lane] = 0.0;
   const bool var = lane < n;
-  double ui = var ? gxg[g * n + lane] : 0.0;  // the running g, u_k = (L^{-1} g)_k from step k on
-  double invLd = var ? 0.0 : 1.0;             // 1 / L[lane][lane] (1 on the padding)
+  double ui = var ? form_gx<FM>(gxg, g * n + lane) : 0.0;  // the running g, u_k = (L^{-1} g)_k from step k on
+  double invLd = var ? 0.0 : 1.0;                           // 1 / L[lane][lane] (1 on the padding)
+  if constexpr (FM == 2) invLd = low ? Hg[fy.ik + lane] : 1.0;
   wave_lds_sync();
+  [[maybe_unused]] bool spd = true;  // FM == 1: every pivot was a positive finite number
 
   // ---- H = L L^T (right-looking, in place) and u = L^{-1} g.  Step k updates
   // the whole rows k+1.. of the symmetric trailing block, the two halves of
   // the wave on alternate columns (the upper triangle is redundant and free:
   // no predicate in the loop; the last trip of the upper half may touch the
   // row's padding word, colk is zero there)
+  if constexpr (FM == 2) {
+    // u alone, by the loop's own operations on the stored L and 1 / L_kk
+    for (int k = 0; k < n; ++k) {
+      const double uk = readlane_d(ui, k) * readlane_d(invLd, k);
+      const double lik = (low && lane > k) ? Lm[i * WS + k] : 0.0;
+      if (lane == k) ui = uk;
+      else if (low && lane > k) ui = __builtin_fma(-lik, uk, ui);
+    }
+  } else  // (the factorisation loop keeps its indentation)
   for (int k = 0; k < n; ++k) {
+    if constexpr (FM == 1) {
+      const double akk = Lm[k * WS + k];
+      spd = spd && akk > 0.0 && akk < kInf;
+    }
     const double ik = rsq(Lm[k * WS + k]);
     const double uk = readlane_d(ui, k) * ik;
     const double lik = i >= k ? Lm[i * WS + k] * ik : 0.0;
@@ -494,6 +639,29 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
 #pragma unroll 4
     for (int jj = 0; jj < trips; ++jj) row[2 * jj] = __builtin_fma(nl, col[2 * jj], row[2 * jj]);
     wave_lds_sync();
+  }
+  if constexpr (FM == 1) {
+    // ---- the factor kernel ends here: every row of D, L's image, the buffer
+    double *fac = gHg;
+    const int found = spd ? QPB_OK : QPB_NOT_SPD;
+    if (lane < bfct::kHdr)
+      fac[lane] = lane == 0 ? (double)found : lane == 1 ? (double)n : lane == 2 ? (double)m : lane == 3 ? 32.0 : 0.0;
+    if (lane == 0 && gbg) *reinterpret_cast<int32_t *>(gbg) = found;
+    // (a row's padding word is never initialised in LDS and never read: zero in the buffer)
+    for (int e = lane; e < bfct::kWaveL; e += 64) fac[fy.L + e] = e % WS == WN ? 0.0 : Lm[e];
+    if (low) fac[fy.ik + lane] = invLd;
+    for (int r = 0; r < m; ++r) {
+      // (the loop of an active row below, for every row)
+      double v = var ? Aq[r * n + lane] : 0.0;
+#pragma unroll
+      for (int k = 0; k < WN; ++k) {
+        const double dk = readlane_d(v * invLd, k);
+        const double lk = (low && lane > k) ? Lm[i * WS + k] : 0.0;
+        v = lane == k ? dk : __builtin_fma(-lk, dk, v);
+      }
+      if (low) fac[fy.D + r * WN + lane] = v;
+    }
+    return;
   }
   if (low) ub[lane] = ui;
   wave_lds_sync();
@@ -528,12 +696,14 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   for (unsigned long long rem = W; rem != 0; rem &= rem - 1ull) {
     const int r = __builtin_ctzll(rem);
     // row r of D: L d^T = a_r^T, component j at lane j (0 on the padding and the upper lanes)
-    double v = var ? Aq[r * n + lane] : 0.0;
+    double v = FM == 2 ? (low ? Hg[fy.D + r * WN + lane] : 0.0) : var ? Aq[r * n + lane] : 0.0;
+    if constexpr (FM != 2) {
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
       const double dk = readlane_d(v * invLd, k);
       const double lk = (low && lane > k) ? Lm[i * WS + k] : 0.0;
       v = lane == k ? dk : __builtin_fma(-lk, dk, v);
+    }
     }
     const double dd = wave_sum(low ? v * v : 0.0);
     double cl = 0.0;  // R[lane][cnt]
@@ -651,6 +821,48 @@ extern "C" hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long str
   qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
     hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), true>), dim3((unsigned)blocks), dim3(64), 0,
                        stream, H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch);
+  });
+  return hipGetLastError();
+}
+
+// qpb_factor_shared_backward: one launch of one workgroup of the class's own
+// kernel in its factor form, on the one H and A
+extern "C" hipError_t qpb_launch_kkt_bwd_factor(int n, int m, const double *H, const double *A, double *bfac,
+                                                int32_t *fstatus, hipStream_t stream) {
+  double *const found = reinterpret_cast<double *>(fstatus);  // the form's one int32 output
+  const double *no_d = nullptr;
+  const uint32_t *no_u = nullptr;
+  const int32_t *no_i = nullptr;
+  double *no_o = nullptr;
+  if (n > 16 || m > 32) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_wave_kernel<false, qpb::bwd::Form<1>>), dim3(1), dim3(64), 0, stream, H, A, no_d, no_d, no_u,
+                       no_i, no_d, bfac, no_o, no_o, found, n, m, 1LL);
+    return hipGetLastError();
+  }
+  qpb::row16::dispatch_form(n, m, [&](auto MR, auto N16, auto) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, qpb::bwd::Form<1>>), dim3(1), dim3(64), 0, stream, H, A,
+                       no_d, no_d, no_u, no_i, no_d, bfac, no_o, no_o, found, n, m, 1LL);
+  });
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_factored_backward: the factored forms on such a buffer
+// (gH and gA are pass 2's)
+extern "C" hipError_t qpb_launch_kkt_bwd_factored(const qpb_desc *d, const double *bfac, const double *x,
+                                                  const double *lam, const uint32_t *active, const int32_t *status,
+                                                  const double *gx, double *gf, double *gb, hipStream_t stream) {
+  const double *no_a = nullptr;
+  double *no_o = nullptr;
+  if (d->n > 16 || d->m > 32) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_wave_kernel<false, qpb::bwd::Form<2>>), dim3((unsigned)d->batch), dim3(64), 0, stream, bfac,
+                       no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m, (long long)d->batch);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, qpb::bwd::Form<2>>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, bfac, no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m,
+                       (long long)d->batch);
   });
   return hipGetLastError();
 }

@@ -91,6 +91,16 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long s
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_sum(const qpb_desc *d, const double *x, const double *dx, const double *gb,
                                                const double *lam, const uint32_t *active, const int32_t *status,
                                                double *slots, double *gH, double *gA, hipStream_t stream);
+// qpb_factor_shared_backward: ONE H and ONE A (NULL at m == 0) into the class's
+// backward buffer (qpb_factor.h, bfct), one small launch of the class's own
+// kernel in its factor form (qpb_kkt_bwd.hip); fstatus may be NULL
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factor(int n, int m, const double *H, const double *A, double *bfac,
+                                                  int32_t *fstatus, hipStream_t stream);
+// qpb_solve_factored_backward, pass 1: qpb_launch_kkt_bwd_shared with both
+// operands shared, on such a buffer (pass 2 is qpb_launch_kkt_bwd_sum unchanged)
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factored(const qpb_desc *d, const double *bfac, const double *x,
+                                                    const double *lam, const uint32_t *active, const int32_t *status,
+                                                    const double *gx, double *gf, double *gb, hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

@@ -170,6 +170,34 @@ static_assert(route_factored(33, 0).step == 0 && route_factored(16, 65).step == 
 static_assert(route_factored(kFactoredMaxN, kFactoredMaxM).step > 0 && route_factored(kFactoredMaxN + 1, 1).step == 0 &&
               route_factored(1, kFactoredMaxM + 1).step == 0);
 
+// qpb_factor_shared_backward and qpb_solve_factored_backward: route_shared_bwd's
+// classes, whose factor form writes and whose factored form reads the class's
+// own layout of the backward's buffer (qpb_factor.h, bfct, decides the class by
+// the same two limits); above them there is neither: step 0, and the calls are
+// unsupported.
+constexpr Route route_factored_bwd(int n, int m) {
+  const Route r = route_shared_bwd(n, m);
+  return {r.kernel, r.step};
+}
+constexpr int kFactoredBwdMaxN = kSharedMaxN, kFactoredBwdMaxM = kSharedMaxM;
+
+static_assert(route_factored_bwd(16, 32).kernel == Kernel::gi_dense &&
+              route_factored_bwd(1, 0).kernel == Kernel::gi_dense);
+static_assert(route_factored_bwd(16, 33).kernel == Kernel::gi_wave &&
+              route_factored_bwd(17, 0).kernel == Kernel::gi_wave &&
+              route_factored_bwd(32, 64).kernel == Kernel::gi_wave);
+static_assert(route_factored_bwd(16, 32).step == 1LL << 27 && route_factored_bwd(32, 64).step == 1LL << 25);
+static_assert(route_factored_bwd(33, 0).step == 0 && route_factored_bwd(16, 65).step == 0 &&
+              route_factored_bwd(128, 256).step == 0);
+static_assert(route_factored_bwd(kFactoredBwdMaxN, kFactoredBwdMaxM).step > 0 &&
+              route_factored_bwd(kFactoredBwdMaxN + 1, 1).step == 0 &&
+              route_factored_bwd(1, kFactoredBwdMaxM + 1).step == 0);
+// a factored forward's outputs go to the factored backward: the same classes and limits
+static_assert(route_factored_bwd(16, 32).kernel == route_factored(16, 32).kernel &&
+              route_factored_bwd(16, 33).kernel == route_factored(16, 33).kernel &&
+              route_factored_bwd(17, 0).kernel == route_factored(17, 0).kernel &&
+              kFactoredBwdMaxN == kFactoredMaxN && kFactoredBwdMaxM == kFactoredMaxM);
+
 // qpb_solve_range with m > 0: the RG forms of the two wavefront-level classes,
 // whatever meq and the shared bits (the forms take both at run time); above
 // them -- the Gram class -- there is no range form yet: step 0, and the call is

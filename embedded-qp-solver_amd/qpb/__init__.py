@@ -98,6 +98,16 @@ _lib.qpb_solve_shared_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32]
 _lib.qpb_solve_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_shared_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_factor_backward_doubles.argtypes = [ctypes.c_int32, ctypes.c_int32]
+_lib.qpb_factor_backward_doubles.restype = ctypes.c_int64
+_lib.qpb_factor_shared_backward.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_vp] * 5
+_lib.qpb_factor_shared_backward.restype = ctypes.c_int
+_lib.qpb_factor_shared_backward_host.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_vp] * 4
+_lib.qpb_factor_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
+_lib.qpb_solve_factored_backward.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
+_lib.qpb_solve_factored_backward_host.restype = ctypes.c_int
 _lib.qpb_solve_range.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 12
 _lib.qpb_solve_range.restype = ctypes.c_int
 _lib.qpb_solve_range_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 11
@@ -777,6 +787,149 @@ def solve_shared_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
     rc = _lib.qpb_solve_shared_backward_host(ctypes.byref(d), shared, p(H), p(A), p(x), p(lam), p(act), p(st), p(gx),
                                              p(gH), p(gf), p(gA), p(gb))
     _check(rc, "qpb_solve_shared_backward_host")
+    return gH, gf, gA, gb
+
+
+class BackwardFactor(NamedTuple):
+    """One shared H and A, factored once for the backward (qpb_factor_shared_backward):
+    the input of ``solve_factored_backward``.  Not a ``SharedFactor``: the buffer
+    is the backward kernels' own."""
+    fac: object     # (factor_backward_doubles(n, m),) float64: L, 1 / L_kk, D = A L^-T, the multipliers (layout internal)
+    n: int
+    m: int
+    status: object  # (1,) int32: OK or NOT_SPD
+
+
+def factor_backward_doubles(n: int, m: int) -> int:
+    """Doubles a backward factor buffer for (n, m) holds (qpb_factor_backward_doubles; n <= 32, m <= 64)."""
+    k = int(_lib.qpb_factor_backward_doubles(int(n), int(m)))
+    if k < 0:
+        _check(k, "qpb_factor_backward_doubles")
+    return k
+
+
+def factor_shared_backward(H, A=None, *, stream=None) -> BackwardFactor:
+    """Factor ONE H (n, n) and ONE A (m, n) for the backward of a whole batch,
+    once (qpb_factor_shared_backward): torch CUDA float64 tensors, one small
+    launch, asynchronous on ``stream``.  The result goes to
+    ``solve_factored_backward`` any number of times.  n <= 32 and m <= 64."""
+    import torch
+    if not H.is_cuda:
+        raise ValueError("qpb.factor_shared_backward expects CUDA (HIP) tensors; use factor_shared_backward_host "
+                         "for numpy")
+    m = 0 if A is None else A.shape[0]
+    for t in (H,) + ((A,) if m else ()):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+        if t.device != H.device:
+            raise ValueError("the inputs must live on the same CUDA device")
+    n = H.shape[-1]
+    if tuple(H.shape) != (n, n) or (m and tuple(A.shape) != (m, n)):
+        raise ValueError("shape mismatch: H must be (n, n) and A (m, n)")
+    fac = torch.empty((factor_backward_doubles(n, m),), dtype=torch.float64, device=H.device)
+    status = torch.empty((1,), dtype=torch.int32, device=H.device)
+    rc = _lib.qpb_factor_shared_backward(n, m, _ptr(H), _ptr(A) if m else None, _ptr(fac), _ptr(status),
+                                         _stream_ptr(stream))
+    _check(rc, "qpb_factor_shared_backward")
+    return BackwardFactor(fac, n, m, status)
+
+
+def solve_factored_backward(F: BackwardFactor, sol: Solution, gx, *, need=NEED_ALL, stream=None):
+    """``solve_shared_backward`` with a 2-D H and A, without the per-QP set-up
+    and without H and A (qpb_solve_factored_backward): ``F`` is
+    ``factor_shared_backward(H, A)``.  Returns (gH (n, n), gf (B, n), gA (m, n),
+    gb (B, m)), each bit for bit what ``solve_shared_backward(H, A, sol, gx)``
+    returns; an entry is None where ``need`` leaves it out, and gA and gb with
+    m == 0."""
+    import torch
+    if not (gx.is_cuda and F.fac.is_cuda):
+        raise ValueError("qpb.solve_factored_backward expects CUDA (HIP) tensors; use solve_factored_backward_host "
+                         "for numpy")
+    n, m = int(F.n), int(F.m)
+    need = _need_set(need)
+    if gx.dtype != torch.float64 or not gx.is_contiguous():
+        raise ValueError("inputs must be contiguous float64")
+    if gx.dim() != 2 or gx.shape[1] != n:
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    B = gx.shape[0]
+    if F.fac.dtype != torch.float64 or tuple(F.fac.shape) != (factor_backward_doubles(n, m),) \
+            or not F.fac.is_contiguous():
+        raise ValueError(f"the backward factor buffer is not one for n={n}, m={m}")
+    if sol.x.device != gx.device or F.fac.device != gx.device:
+        raise ValueError("the inputs must live on the factor's CUDA device")
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if m and (sol.lam is None or sol.lam.dtype != torch.float64 or not sol.lam.is_contiguous()
+              or sol.lam.shape != (B, m)):
+        raise ValueError("sol.lam must be a contiguous float64 tensor of shape (B, m)")
+    if m and (not sol.active.is_contiguous() or sol.active.shape != (B, (m + 31) // 32)
+              or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(m/32)) tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(n, n) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    gA = new(m, n) if m and "A" in need else None
+    gb = new(B, m) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None  # m == 0 and only A / b wanted
+    d = Desc(n, m, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_factored_backward(ctypes.byref(d), _ptr(F.fac), _ptr(sol.x), _ptr(sol.lam) if m else None,
+                                          _ptr(sol.active) if m else None, _ptr(sol.status), _ptr(gx), _ptr(gH),
+                                          _ptr(gf), _ptr(gA), _ptr(gb), _stream_ptr(stream))
+    _check(rc, "qpb_solve_factored_backward")
+    return gH, gf, gA, gb
+
+
+def factor_shared_backward_host(H, A=None) -> BackwardFactor:
+    """numpy in / numpy out (qpb_factor_shared_backward_host): ``factor_shared_backward`` with host arrays."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    m = 0 if A is None else A.shape[0]
+    n = H.shape[-1]
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+    if H.shape != (n, n) or (m and A.shape != (m, n)):
+        raise ValueError("shape mismatch: H must be (n, n) and A (m, n)")
+    fac = np.zeros(factor_backward_doubles(n, m))
+    st = np.zeros(1, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_factor_shared_backward_host(n, m, p(H), p(A) if m else None, p(fac), p(st))
+    _check(rc, "qpb_factor_shared_backward_host")
+    return BackwardFactor(fac, n, m, st)
+
+
+def solve_factored_backward_host(F: BackwardFactor, sol: Solution, gx, *, need=NEED_ALL):
+    """numpy in / numpy out (qpb_solve_factored_backward_host): ``solve_factored_backward`` with host arrays."""
+    import numpy as np
+    need = _need_set(need)
+    n, m = int(F.n), int(F.m)
+    fac = np.ascontiguousarray(F.fac, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B = gx.shape[0]
+    lam = act = None
+    if m:
+        lam = np.ascontiguousarray(sol.lam, dtype=np.float64)
+        act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    if gx.shape != (B, n) or x.shape != (B, n) or fac.shape != (factor_backward_doubles(n, m),) \
+            or (m and (lam.shape != (B, m) or act.shape != (B, (m + 31) // 32))):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros((n, n)) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    gA = np.zeros((m, n)) if m and "A" in need else None
+    gb = np.zeros((B, m)) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None
+    d = Desc(n, m, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_factored_backward_host(ctypes.byref(d), p(fac), p(x), p(lam), p(act), p(st), p(gx), p(gH),
+                                               p(gf), p(gA), p(gb))
+    _check(rc, "qpb_solve_factored_backward_host")
     return gH, gf, gA, gb
 
 

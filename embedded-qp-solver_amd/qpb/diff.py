@@ -15,8 +15,10 @@ the weights of a QP layer, with f and b from the network's input: the solve is
 is (n, n), and no (B, n, n) or (B, m, n) tensor is ever allocated.  With
 ``prefactor=True`` (a 2-D H and, when there are rows, a 2-D A) the forward
 factors the two once, ``qpb.factor_shared``, and solves with
-``qpb.solve_factored``: the per-QP set-up is gone from the forward; the
-backward is the same ``qpb.solve_shared_backward``.
+``qpb.solve_factored``, and the backward factors the saved H and A once,
+``qpb.factor_shared_backward``, and runs ``qpb.solve_factored_backward``: the
+per-QP set-up is gone from both passes.  The gradients are bit for bit those of
+``qpb.solve_shared_backward``; a forward without gradients pays nothing for them.
 
 ``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
 and ub (``qpb.solve_box_backward``, n <= 32).
@@ -25,13 +27,23 @@ and ub (``qpb.solve_box_backward``, n <= 32).
 H, f, A, bl and bu: the backward is ``qpb.solve_backward`` (or the shared one)
 on the range solve's outputs, its ``gb`` routed to ``bl`` or ``bu`` by the
 ``lower`` bits.  ``prefactor=True`` (a 2-D H and a 2-D A) factors once per
-forward and solves with ``qpb.solve_range_factored``; the backward is unchanged.
+forward and solves with ``qpb.solve_range_factored``; the backward is the
+factored one in the same way.
 """
 from __future__ import annotations
 
 import torch
 
 import qpb
+
+
+def _backward(ctx, H, A, sol, gx, wanted):
+    """The backward call of a forward: on a prefactored forward the saved H and A
+    are factored once for the backward and neither is read per QP."""
+    if ctx.prefactor:
+        return qpb.solve_factored_backward(qpb.factor_shared_backward(H, A), sol, gx, need=wanted)
+    backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
+    return backward(H, A, sol, gx, need=wanted)
 
 
 class QPFunction(torch.autograd.Function):
@@ -51,6 +63,7 @@ class QPFunction(torch.autograd.Function):
             sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol) if A is not None \
                 else qpb.solve(H, f, max_iter=max_iter, feas_tol=feas_tol)
         ctx.has_rows = A is not None
+        ctx.prefactor = prefactor
         ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.status)
         ctx.mark_non_differentiable(sol.status)
         return sol.x, sol.status
@@ -63,8 +76,7 @@ class QPFunction(torch.autograd.Function):
             return (None,) * 8
         sol = qpb.Solution(x, lam, active, status, None)
         # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
-        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
-        gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
+        gH, gf, gA, gb = _backward(ctx, H, A, sol, gx.contiguous(), wanted)
         return gH, gf, gA, gb, None, None, None, None
 
 
@@ -110,6 +122,7 @@ class RangeQPFunction(torch.autograd.Function):
         else:
             sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
         ctx.shared = H.dim() == 2 or A.dim() == 2
+        ctx.prefactor = prefactor
         ctx.meq = meq
         ctx.has = (True, True, True, bl is not None, bu is not None)
         ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.lower, sol.status)
@@ -124,8 +137,7 @@ class RangeQPFunction(torch.autograd.Function):
         if not wanted:
             return (None,) * 9
         sol = qpb.Solution(x, lam, active, status, None)
-        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
-        gH, gf, gA, gb = backward(H, A, sol, gx.contiguous(), need=wanted)
+        gH, gf, gA, gb = _backward(ctx, H, A, sol, gx.contiguous(), wanted)
         gbl = gbu = None
         if gb is not None:
             # every element of gb goes to the bound its row is active at: bl where the
@@ -153,9 +165,10 @@ def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: f
     that the forward raises ``QPBError(ERR_UNSUPPORTED)``.  ``prefactor=True``
     needs a 2-D H and a 2-D A, else ValueError: the forward factors them once
     (``qpb.factor_shared``) and solves with ``qpb.solve_range_factored``, whose
-    x may differ from the default's by rounding; the backward is the same
-    ``qpb.solve_shared_backward`` on H and A.  The default is today's call, bit
-    for bit."""
+    x may differ from the default's by rounding; the backward factors H and A
+    once (``qpb.factor_shared_backward``) and runs ``qpb.solve_factored_backward``,
+    bit for bit ``qpb.solve_shared_backward`` on H and A.  The default is today's
+    call, bit for bit."""
     if prefactor:
         if H.dim() != 2 or A.dim() != 2:
             raise ValueError("prefactor=True needs a 2-D H (n, n) and a 2-D A (m, n): one matrix for the batch")
@@ -185,8 +198,10 @@ def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: fl
     batch, computed without a per-QP copy.  ``prefactor=True`` needs a 2-D H
     and (when there are rows) a 2-D A, else ValueError: the forward factors
     them once (``qpb.factor_shared``) and solves with ``qpb.solve_factored``,
-    whose x may differ from the default's by rounding; the backward is the
-    same.  The default is today's call, bit for bit."""
+    whose x may differ from the default's by rounding; the backward factors
+    them once as well (``qpb.factor_shared_backward``,
+    ``qpb.solve_factored_backward``), with the default's gradients bit for bit.
+    The default is today's call, bit for bit."""
     if prefactor:
         if H.dim() != 2 or (A is not None and A.dim() != 2):
             raise ValueError("prefactor=True needs a 2-D H (n, n) and, with rows, a 2-D A (m, n): one matrix for the batch")

@@ -18,6 +18,7 @@
  *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
+ *   ... differentiated on the H and A factored once           qpb_factor_shared_backward, qpb_solve_factored_backward
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -395,9 +396,10 @@ int qpb_factor_shared_host(int32_t n, int32_t m, const double *H,
  * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
  * missing pointers QPB_ERR_INVALID_ARG (fac, f, x and status always; b, lam and
  * active with m > 0; iters may be NULL); a missing device last.
- * Follow-ups: a factored qpb_solve_shared_backward (kkt_bwd re-factors H and
- * re-forms A_W L^-T per QP) and a shared H with a per-QP A.  Two-sided rows on
- * the same buffer: qpb_solve_range_factored, below.
+ * The backward without the per-QP set-up is qpb_solve_factored_backward, below,
+ * on a buffer of its own (qpb_factor_shared_backward).  Follow-up: a shared H
+ * with a per-QP A.  Two-sided rows on the same buffer:
+ * qpb_solve_range_factored, below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_factored(const qpb_desc *desc, int32_t meq, const double *fac,
 		       const double *f, const double *b, double *x, double *lam,
@@ -572,9 +574,10 @@ int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
  * missing pointers QPB_ERR_INVALID_ARG (fac, f, x and status always; with m > 0
  * lam, active and at least one of bl and bu; lower and iters may be NULL); a fac
  * that is not 16-byte aligned QPB_ERR_INVALID_ARG; a missing device last.
- * Limits as qpb_solve_factored.  Follow-ups: a factored
- * qpb_solve_shared_backward for the same buffer (the backward of this call is
- * qpb_solve_shared_backward on H and A, unchanged), and the Gram class.
+ * Limits as qpb_solve_factored.  The backward of this call is
+ * qpb_solve_shared_backward on H and A, or, without the per-QP set-up,
+ * qpb_solve_factored_backward on the backward's own buffer, below.  Follow-up:
+ * the Gram class.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_range_factored(const qpb_desc *desc, int32_t meq,
 			     const double *fac, const double *f,
@@ -589,6 +592,101 @@ int qpb_solve_range_factored_host(const qpb_desc *desc, int32_t meq,
 				  double *lam, uint32_t *active,
 				  uint32_t *lower, int32_t *status,
 				  int32_t *iters);
+
+/* The backward of a solve on one H and one A, factored ONCE.
+ * qpb_solve_shared_backward(shared = QPB_SHARED_H | QPB_SHARED_A) factors the
+ * same H and re-forms A_W L^-T for every QP; everything its kernels compute from
+ * H and A alone is the same numbers for the whole batch.
+ * qpb_factor_shared_backward computes them once into a buffer of the backward's
+ * own, `bfac`, and qpb_solve_factored_backward starts every QP from it.
+ *
+ * `bfac` is NOT qpb_factor_shared's `fac`: it is written by the backward
+ * kernels' own set-up (the forward's D of the n <= 16 class comes from another
+ * sweep), and it holds L, 1 / L_kk, D = A L^-T and, in the
+ * n <= 16 class, the sweep's elimination multipliers -- neither H nor A: no
+ * output reads them.  What remains per QP is the unfactored kernel's operations
+ * on the unfactored kernel's numbers, so the outputs are that call's bit for
+ * bit.  The layout is internal (csrc/qpb_factor.h) and belongs
+ * to one (n, m): a buffer made for another shape, or a forward `fac` passed
+ * here, is the caller's error, like any wrongly sized array.  `bfac` must be
+ * 16-byte aligned (hipMalloc's and torch's allocations are), else
+ * QPB_ERR_INVALID_ARG. */
+
+/* doubles a backward buffer for (n, m) holds; < 0: a qpb_error (n < 1, m < 0:
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64: QPB_ERR_UNSUPPORTED).  Pure host
+ * arithmetic. */
+int64_t qpb_factor_backward_doubles(int32_t n, int32_t m);
+
+/* Factor ONE H (n x n) and ONE A (m x n; NULL with m == 0) into `bfac`
+ * (qpb_factor_backward_doubles(n, m) doubles, device), every element of which
+ * is written.  One small launch, asynchronous on `stream`: a solve queued behind
+ * it on the same stream needs no host synchronisation.  fstatus (one int32,
+ * device, may be NULL): QPB_OK, or QPB_NOT_SPD when a pivot is not a positive
+ * finite number.  The rows of A are not judged: the backward never judges them.
+ * Errors, in order: n < 1 or m < 0 QPB_ERR_INVALID_ARG; n > 32 or m > 64
+ * QPB_ERR_UNSUPPORTED; H or bfac missing, or A missing with m > 0,
+ * QPB_ERR_INVALID_ARG; a bfac that is not 16-byte aligned QPB_ERR_INVALID_ARG;
+ * a missing device last. */
+int qpb_factor_shared_backward(int32_t n, int32_t m, const double *H,
+			       const double *A, double *bfac, int32_t *fstatus,
+			       void *stream);
+
+/* Same with host pointers; bfac (host) receives the buffer. */
+int qpb_factor_shared_backward_host(int32_t n, int32_t m, const double *H,
+				    const double *A, double *bfac,
+				    int32_t *fstatus);
+
+/* qpb_solve_shared_backward(shared = QPB_SHARED_H | QPB_SHARED_A) without H and
+ * A, on a buffer of qpb_factor_shared_backward for (desc->n, desc->m).  Every
+ * non-NULL output equals, bit for bit, what that call writes for the same x,
+ * lam, active, status and gx on the H and A the buffer was made from.  Its
+ * contract, restated:
+ *   gH (n x n)      ONE matrix, 1/2 sum_k (dx_k x_k^T + x_k dx_k^T) over the
+ *                   batch, symmetric bit for bit.
+ *   gA (m x n)      ONE matrix, the sum over the batch of qpb_solve_backward's
+ *                   per-QP gA.
+ *   gf (B x n), gb (B x m)   per QP, qpb_solve_backward's.
+ *   gH, gf, gA, gb  each may be NULL; at least one must be given.
+ *   status          may be NULL: every QP counts as QPB_OK.  A QP whose status
+ *                   is not QPB_OK gets zeros in gf and gb and contributes
+ *                   exactly 0 to the sums, even where its x or lam holds NaN.
+ *   lam, active     lam outside W is ignored, whatever it holds; bits >= m are
+ *                   ignored.  Weakly active rows, dependent rows and masks with
+ *                   more than n bits are treated as in qpb_solve_backward.
+ *   m == 0          gA and gb are ignored.
+ *   workspace       what qpb_solve_shared_backward takes with both operands
+ *                   shared: the slots, B n doubles when gf is NULL, B m doubles
+ *                   when gA is wanted and gb is NULL.
+ *   reproducible    the summed outputs' bits depend on the inputs and on
+ *                   (n, m, batch) only, as qpb_solve_shared_backward's.
+ * A buffer whose H was not SPD gives zeros in every non-NULL output of every
+ * QP, whatever `status` says (x and the lam in W finite, as for any QP that
+ * counts as QPB_OK).  The buffer is only read: any number of calls, on any
+ * streams, may use it at once.
+ * Pass 1 is the factored forms of qpb_kkt_bwd.hip -- no Cholesky, no sweep and
+ * no per-row substitution per QP -- and pass 2 the sums of
+ * qpb_solve_shared_backward, unchanged.
+ * Errors, in order: the descriptor as qpb_solve; desc->flags != 0
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64 QPB_ERR_UNSUPPORTED; batch == 0 returns
+ * 0 before the pointers are looked at; missing pointers QPB_ERR_INVALID_ARG
+ * (bfac, x and gx always; lam and active with m > 0; at least one output); a
+ * bfac that is not 16-byte aligned QPB_ERR_INVALID_ARG; a missing device last.
+ * Limits as qpb_solve_factored.  Follow-ups: the Gram class, a shared H with a
+ * per-QP A, a factored qpb_solve_box_backward.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_factored_backward(const qpb_desc *desc, const double *bfac,
+				const double *x, const double *lam,
+				const uint32_t *active, const int32_t *status,
+				const double *gx, double *gH, double *gf,
+				double *gA, double *gb, void *stream);
+
+/* Same with host pointers (bfac included: the call uploads it). */
+int qpb_solve_factored_backward_host(const qpb_desc *desc, const double *bfac,
+				     const double *x, const double *lam,
+				     const uint32_t *active,
+				     const int32_t *status, const double *gx,
+				     double *gH, double *gf, double *gA,
+				     double *gb);
 
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
