@@ -31,13 +31,23 @@ using namespace row16;
 
 // N16: n == 16 (coalesced H loads through an LDS transpose); otherwise the
 // rows are padded with the identity and the padded variables get no bounds
-template <bool N16>
+// SH (qpb_solve_box_shared): the QP stride of H, in doubles, is the one
+// trailing argument that only this form has, the run-time strideH -- 0 for one
+// H that the whole batch shares, or n n.  H is read through the QP's base
+// pointer alone (the N16 form's coalesced 16-byte loads and LDS transpose are
+// the same code on the one matrix: every QP of the wave then reads the same two
+// rows per instruction), so the outputs are the other form's bit for bit.
+// Without SH the pack is empty, and the signature and the code object stay as
+// they were.
+template <bool N16, bool SH = false, class... STR>
 __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict__ Hg, const double *__restrict__ fg,
                                                        const double *__restrict__ lbg, const double *__restrict__ ubg,
                                                        double *__restrict__ xg, double *__restrict__ lamg,
                                                        uint32_t *__restrict__ actg, int32_t *__restrict__ statg,
                                                        int32_t *__restrict__ itg, int n, long long batch,
-                                                       int max_iter, double feas_tol) {
+                                                       int max_iter, double feas_tol, STR... strideH) {
+  static_assert(sizeof...(STR) == (SH ? 1 : 0) && (std::is_same_v<STR, long long> && ...),
+                "the shared form alone takes the stride");
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -52,7 +62,11 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   // ------------------------------------------------------------------ load
   const bool var = N16 || l < n;  // lane l carries variable l
   const int lc = var ? l : n - 1;
-  const double *Hq = Hg + g * (long long)n * n;
+  const double *Hq;
+  if constexpr (SH)
+    Hq = Hg + g * (strideH + ...);
+  else
+    Hq = Hg + g * (long long)n * n;
   const double fv = fg[g * n + lc];
   const double ubv = ubg ? ubg[g * n + lc] : kInf;
   const double lbv = lbg ? lbg[g * n + lc] : -kInf;
@@ -392,5 +406,20 @@ extern "C" hipError_t qpb_launch_gi_box(const qpb_desc *d, const double *H, cons
   const auto kernel = d->n == 16 ? qpb::box::gi_box_kernel<true> : qpb::box::gi_box_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x, lam, active, status,
                      iters, d->n, (long long)d->batch, max_iter, tol);
+  return hipGetLastError();
+}
+
+// qpb_solve_box_shared for n <= 16: the SH forms, H's QP stride at run time (0:
+// one copy for the batch, or n n)
+extern "C" hipError_t qpb_launch_gi_box_shared(const qpb_desc *d, const double *H, const double *f, const double *lb,
+                                               const double *ub, double *x, double *lam, uint32_t *active,
+                                               int32_t *status, int32_t *iters, long long strideH,
+                                               hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::box::QPB - 1) / qpb::box::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const auto kernel = d->n == 16 ? qpb::box::gi_box_kernel<true, true, long long>
+                                 : qpb::box::gi_box_kernel<false, true, long long>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x, lam, active, status,
+                     iters, d->n, (long long)d->batch, max_iter, tol, strideH);
   return hipGetLastError();
 }

@@ -415,12 +415,22 @@ struct Rows {
 // Ag = lb, bg = ub (n per QP, either may be NULL: absent bounds), m = 2n; the
 // rows of A are generated where they are loaded (D = A L^{-T} is formed as for
 // a dense A; nothing else reads A)
-template <bool STAMP, bool BOX = false>
+// SH (qpb_solve_box_shared, on BOX): the QP stride of H, in doubles, is the one
+// trailing argument that only this form has, the run-time strideH -- 0 for one
+// H that the whole batch shares, or n n; the one place Hq is formed takes it.
+// The persistent workgroup factors the same H again for every QP it takes, on
+// purpose: the outputs are the BOX form's bit for bit, and that is the test
+// (factoring a shared H once is a follow-up).  Without SH the pack
+// is empty, and the signatures and the code objects stay as they were.
+template <bool STAMP, bool BOX = false, bool SH = false, class... STR>
 __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
     const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
-    double feas_tol, int *__restrict__ queue, double *__restrict__ scratch, unsigned long long *__restrict__ dbg) {
+    double feas_tol, int *__restrict__ queue, double *__restrict__ scratch, unsigned long long *__restrict__ dbg,
+    STR... strideH) {
+  static_assert((!SH || (BOX && !STAMP)) && sizeof...(STR) == (SH ? 1 : 0) && (std::is_same_v<STR, long long> && ...),
+                "the shared form is the BOX kernel's, and it alone takes the stride");
   __shared__ double lds[LDS_D];
   // diagnostic build: s_memrealtime section stamps (0 Cholesky, 1 D, 2 y and
   // s, 3 select + v, 4 r + ratio, 5 w, 6 step + update, 7 outputs, 8 L again,
@@ -459,7 +469,11 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
     __syncthreads();
     const long long g = flags[1];
     if (g >= batch) break;
-    const double *Hq = Hg + g * (long long)n * n;
+    const double *Hq;
+    if constexpr (SH)
+      Hq = Hg + g * (strideH + ...);
+    else
+      Hq = Hg + g * (long long)n * n;
     // BOX: A is implicit and Ag holds lb (n per QP, maybe NULL), so no A row exists to point at: Aq is null
     // there, and its one read is in the !BOX branch of the setup
     const double *Aq = BOX ? nullptr : Ag + g * (long long)m * n;
@@ -1033,10 +1047,11 @@ __global__ __launch_bounds__(NT, 1) void gi_gram_kernel(
 }  // namespace qpb
 
 // scratch: per workgroup (NB - QL) D_W rows beyond the LDS ones + the queue head
-template <bool BOX>
+template <bool BOX, class... STR>
 static hipError_t launch_gi_gram(const qpb_desc *d, const double *H, const double *f, const double *A,
                                  const double *b, double *x, double *lam, uint32_t *active, int32_t *status,
-                                 int32_t *iters, unsigned long long *sections, hipStream_t stream) {
+                                 int32_t *iters, unsigned long long *sections, hipStream_t stream, STR... strideH) {
+  constexpr bool SH = sizeof...(STR) == 1;
   const auto [max_iter, tol] = qpb_resolve_limits(d);
   int dev = 0, cus = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -1050,16 +1065,16 @@ static hipError_t launch_gi_gram(const qpb_desc *d, const double *H, const doubl
     int *queue = reinterpret_cast<int *>(static_cast<char *>(buf) + rows_bytes);
     hipError_t err = hipMemsetAsync(queue, 0, sizeof(int), stream);
     if (err != hipSuccess) return err;
-    if constexpr (!BOX)  // the stamped diagnostic build exists for the dense form only
+    if constexpr (!BOX && !SH)  // the stamped diagnostic build exists for the dense form only
       if (sections) {
         hipLaunchKernelGGL((qpb::gram::gi_gram_kernel<true, BOX>), dim3((unsigned)grid), dim3(qpb::gram::NT), 0, stream, H,
                          f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol,
                          queue, static_cast<double *>(buf), sections);
         return hipGetLastError();
       }
-    hipLaunchKernelGGL((qpb::gram::gi_gram_kernel<false, BOX>), dim3((unsigned)grid), dim3(qpb::gram::NT), 0, stream, H,
-                         f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter, tol,
-                         queue, static_cast<double *>(buf), nullptr);
+    hipLaunchKernelGGL((qpb::gram::gi_gram_kernel<false, BOX, SH, STR...>), dim3((unsigned)grid), dim3(qpb::gram::NT), 0,
+                       stream, H, f, A, b, x, lam, active, status, iters, d->n, d->m, (long long)d->batch, max_iter,
+                       tol, queue, static_cast<double *>(buf), nullptr, strideH...);
     return hipGetLastError();
   });
 }
@@ -1075,4 +1090,12 @@ extern "C" hipError_t qpb_launch_gi_gram_box(const qpb_desc *d, const double *H,
                                              const double *ub, double *x, double *lam, uint32_t *active,
                                              int32_t *status, int32_t *iters, hipStream_t stream) {
   return launch_gi_gram<true>(d, H, f, lb, ub, x, lam, active, status, iters, nullptr, stream);
+}
+// qpb_solve_box_shared for 32 < n <= 128: the BOX + SH form, H's QP stride at run
+// time (0: one copy for the batch, or n n)
+extern "C" hipError_t qpb_launch_gi_gram_box_shared(const qpb_desc *d, const double *H, const double *f,
+                                                    const double *lb, const double *ub, double *x, double *lam,
+                                                    uint32_t *active, int32_t *status, int32_t *iters,
+                                                    long long strideH, hipStream_t stream) {
+  return launch_gi_gram<true>(d, H, f, lb, ub, x, lam, active, status, iters, nullptr, stream, strideH);
 }

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   static_assert(!(FO || FI) || (!(STAMP || REDO || BOX || SH) && (!FO || !EQ)),
                 "the factor forms are the plain or the EQ kernel's");
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
-  static_assert(!SH || !(STAMP || REDO || BOX), "the shared form is the plain or the EQ kernel's");
+  static_assert(!SH || !(STAMP || REDO), "the shared form is the plain, the EQ or the BOX kernel's");
   static_assert(!RG || (EQ && SH != RF && sizeof...(RGA) == 1),
                 "the range form is built on the EQ form and the shared or the factored one, with one trailing argument");
   __shared__ double lds[SLOT];
@@ -197,7 +197,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double *xsd = lds + OFF_X;   // s_p, |D[p,:]|^2
 
   const double *Hq = FI ? facg : SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
-  // BOX: Ag = lb, bg = ub (n per QP, either may be NULL), m = 2n
+  // BOX: Ag = lb, bg = ub (n per QP, either may be NULL), m = 2n; Aq and bq
+  // alias Hq (BOX + SH, qpb_solve_box_shared: only QPB_SHARED_H means anything,
+  // and the bounds stay per QP -- they are read through Ag and bg at g)
   const double *Aq = FI       ? facg + fct::layout(n, m).A
                      : BOX    ? Hq
                      : m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n)
@@ -1039,6 +1041,20 @@ extern "C" hipError_t qpb_launch_gi_wave_box(const qpb_desc *d, const double *H,
                                              const double *ub, double *x, double *lam, uint32_t *active,
                                              int32_t *status, int32_t *iters, hipStream_t stream) {
   return launch_gi_wave<3, false, false, true>(d, H, f, lb, ub, x, lam, active, status, iters, stream);
+}
+
+// qpb_solve_box_shared for 16 < n <= 32: the BOX + SH form, H's QP stride 0 (one
+// copy for the batch; the bit rides in m as the SH form's does) or n n
+extern "C" hipError_t qpb_launch_gi_wave_box_shared(const qpb_desc *d, const double *H, const double *f,
+                                                    const double *lb, const double *ub, double *x, double *lam,
+                                                    uint32_t *active, int32_t *status, int32_t *iters,
+                                                    long long strideH, hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const int mm = d->m | ((strideH == 0 ? QPB_SHARED_H : 0) << qpb::wv::kShShift);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, true, false, true>), dim3((unsigned)d->batch), dim3(64),
+                     0, stream, H, f, lb, ub, x, lam, active, status, iters, d->n, mm, (long long)d->batch, max_iter,
+                     tol, nullptr);
+  return hipGetLastError();
 }
 
 // qpb_solve_shared for the n <= 32, m <= 64 class: a QP stride of 0 (one copy

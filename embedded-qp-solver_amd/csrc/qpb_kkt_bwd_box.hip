@@ -51,11 +51,23 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
 
 // N16: n == 16 (coalesced loads and stores through this QP's LDS slot);
 // otherwise the rows are padded with the identity.
-template <bool N16>
+// SH (pass 1 of qpb_solve_box_shared_backward, both kernels): the QP stride of
+// H, in doubles, is the one trailing argument that only this form has, the
+// run-time strideH -- 0 for one H that the whole batch shares, or n n.  The
+// masked factorisation differs per QP and stays per QP; only the address of H
+// changes, so gf, glb and gub are the other form's bit for bit.  The form's
+// gHg is per QP like the other's (pass 1 passes NULL: the sum is pass 2's).
+// Without SH the pack is empty: the signatures and code objects stay.
+template <bool SH, class... STR>
+inline constexpr bool stride_pack_ok = sizeof...(STR) == (SH ? 1 : 0) && (std::is_same_v<STR, long long> && ...);
+
+template <bool N16, bool SH = false, class... STR>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
-    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch) {
+    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
+    STR... strideH) {
+  static_assert(stride_pack_ok<SH, STR...>, "the shared form alone takes the stride");
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -68,7 +80,11 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   // ------------------------------------------------------------------ load
   const bool var = N16 || l < n;
   const int lc = var ? l : n - 1;
-  const double *Hq = Hg + g * (long long)n * n;
+  const double *Hq;
+  if constexpr (SH)
+    Hq = Hg + g * (strideH + ...);
+  else
+    Hq = Hg + g * (long long)n * n;
   const bool ok = statg ? statg[g] == QPB_OK : true;
   // a QP that is not QPB_OK has no fixed variable and stores zeros
   const uint32_t W = ok ? actg[g] : 0u;
@@ -190,10 +206,13 @@ constexpr int W_L = 0, W_H = WN * WS, W_X = 2 * WN * WS, W_DX = W_X + 32, W_SIZE
 constexpr int W_COL = WN + 2;  // the pivot column of a factorisation step, zero past the matrix
 static_assert((W_SIZE + W_COL) * 8 <= 20480, "8 waves per CU by LDS");
 
+template <bool SH = false, class... STR>
 __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
-    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch) {
+    double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
+    STR... strideH) {
+  static_assert(stride_pack_ok<SH, STR...>, "the shared form alone takes the stride");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -203,7 +222,11 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
   const bool low = lane < WN;      // the lanes that carry a component
   const long long g = blockIdx.x;  // one workgroup of one wave per QP: always < batch
   double *Lm = lds + W_L, *Hm = lds + W_H, *X = lds + W_X, *DX = lds + W_DX;
-  const double *Hq = Hg + g * (long long)n * n;
+  const double *Hq;
+  if constexpr (SH)
+    Hq = Hg + g * (strideH + ...);
+  else
+    Hq = Hg + g * (long long)n * n;
   const bool ok = statg ? statg[g] == QPB_OK : true;
   // The active mask as one 64-bit word (wave-uniform): 16 < n, so 2n bits
   // take two words, and bit n + j of a lower bound crosses from word 0 into
@@ -309,8 +332,8 @@ extern "C" hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H,
                                              double *gH, double *gf, double *glb, double *gub, hipStream_t stream) {
   using namespace qpb::bwdbox;
   if (d->n > 16) {  // one workgroup of one wave per QP
-    hipLaunchKernelGGL(kkt_bwd_box_wave_kernel, dim3((unsigned)d->batch), dim3(64), 0, stream, H, x, active, status, gx,
-                       gH, gf, glb, gub, d->n, (long long)d->batch);
+    hipLaunchKernelGGL(kkt_bwd_box_wave_kernel<>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, x, active, status,
+                       gx, gH, gf, glb, gub, d->n, (long long)d->batch);
     return hipGetLastError();
   }
   const long long blocks = (d->batch + QPB - 1) / QPB;
@@ -320,5 +343,27 @@ extern "C" hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H,
   else
     hipLaunchKernelGGL(kkt_bwd_box_dense_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, stream, H, x, active,
                        status, gx, gH, gf, glb, gub, d->n, (long long)d->batch);
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_box_shared_backward: the SH forms, H's QP stride at run
+// time (0: one copy for the batch, or n n); gH, where given, is per QP
+extern "C" hipError_t qpb_launch_kkt_bwd_box_shared(const qpb_desc *d, long long strideH, const double *H,
+                                                    const double *x, const uint32_t *active, const int32_t *status,
+                                                    const double *gx, double *gH, double *gf, double *glb,
+                                                    double *gub, hipStream_t stream) {
+  using namespace qpb::bwdbox;
+  if (d->n > 16) {
+    hipLaunchKernelGGL((kkt_bwd_box_wave_kernel<true, long long>), dim3((unsigned)d->batch), dim3(64), 0, stream, H, x,
+                       active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, strideH);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + QPB - 1) / QPB;
+  if (d->n == 16)
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<true, true, long long>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                       H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, strideH);
+  else
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<false, true, long long>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                       H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, strideH);
   return hipGetLastError();
 }

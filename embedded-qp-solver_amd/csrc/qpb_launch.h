@@ -41,6 +41,21 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd(const qpb_desc *d, const double *H, c
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box(const qpb_desc *d, const double *H, const double *x,
                                                const uint32_t *active, const int32_t *status, const double *gx,
                                                double *gH, double *gf, double *glb, double *gub, hipStream_t stream);
+// qpb_solve_box_shared: the box launchers with H's QP stride in doubles at run
+// time (0: one copy for the whole batch, else n n) -- the SH forms of the three
+// box kernels
+typedef hipError_t qpb_gi_box_shared_launcher(const qpb_desc *d, const double *H, const double *f, const double *lb,
+                                              const double *ub, double *x, double *lam, uint32_t *active,
+                                              int32_t *status, int32_t *iters, long long strideH, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_box_shared_launcher qpb_launch_gi_box_shared,  // n <= 16 (qpb_gi_box.hip)
+    qpb_launch_gi_wave_box_shared,                                 // ... n <= 32 (qpb_gi_wave.hip)
+    qpb_launch_gi_gram_box_shared;                                 // ... n <= 128 (qpb_gi_gram.hip)
+// qpb_solve_box_shared_backward, pass 1: qpb_launch_kkt_bwd_box with that stride
+// (gH NULL: pass 2, qpb_launch_kkt_bwd_sum with m == 0, sums the gradient)
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box_shared(const qpb_desc *d, long long strideH, const double *H,
+                                                      const double *x, const uint32_t *active, const int32_t *status,
+                                                      const double *gx, double *gH, double *gf, double *glb,
+                                                      double *gub, hipStream_t stream);
 // qpb_solve_shared: H and A with run-time QP strides in doubles (0: one copy for
 // the whole batch, else n n and m n); meq == 0 is the plain form, meq > 0 the EQ form
 typedef hipError_t qpb_gi_shared_launcher(const qpb_desc *d, int meq, long long strideH, long long strideA,

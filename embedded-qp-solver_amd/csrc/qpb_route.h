@@ -126,6 +126,28 @@ static_assert(route_bwd_box(kBwdBoxMaxN).step > 0 && route_bwd_box(kBwdBoxMaxN +
 static_assert(route_bwd_box(16).kernel == route(16, 32, 0, true).kernel &&
               route_bwd_box(17).kernel == route(17, 34, 0, true).kernel);
 
+// qpb_solve_box_shared: qpb_solve_box's own route at every shape it takes -- each
+// of the three box kernels has an SH form; qpb_solve_box_shared_backward:
+// route_bwd_box, with its limit.
+constexpr Route route_box_shared(int n) { return route(n, 2 * n, 0, true); }
+constexpr Route route_bwd_box_shared(int n) { return route_bwd_box(n); }
+
+static_assert(route_box_shared(1).kernel == Kernel::gi_box && route_box_shared(16).kernel == Kernel::gi_box);
+static_assert(route_box_shared(17).kernel == Kernel::gi_wave_box && route_box_shared(32).kernel == Kernel::gi_wave_box);
+static_assert(route_box_shared(33).kernel == Kernel::gi_gram_box && route_box_shared(128).kernel == Kernel::gi_gram_box);
+// both name the unshared call's class and step
+static_assert(route_box_shared(16).kernel == route(16, 32, 0, true).kernel &&
+              route_box_shared(16).step == route(16, 32, 0, true).step &&
+              route_box_shared(32).kernel == route(32, 64, 0, true).kernel &&
+              route_box_shared(32).step == route(32, 64, 0, true).step &&
+              route_box_shared(128).kernel == route(128, 256, 0, true).kernel &&
+              route_box_shared(128).step == route(128, 256, 0, true).step);
+static_assert(route_bwd_box_shared(16).kernel == route_bwd_box(16).kernel &&
+              route_bwd_box_shared(16).step == route_bwd_box(16).step &&
+              route_bwd_box_shared(32).kernel == route_bwd_box(32).kernel &&
+              route_bwd_box_shared(32).step == route_bwd_box(32).step &&
+              route_bwd_box_shared(kBwdBoxMaxN + 1).step == 0);
+
 // qpb_solve_shared with a shared H or A (and any meq): route_eq, the SH forms
 // of the two wavefront-level classes; above them -- the Gram class -- there is
 // no shared form yet: step 0, and the call is unsupported.

@@ -16,6 +16,8 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve_shared(H, f, A, b, meq) -> qpb_solve_shared (a 2-D H and / or A: one matrix for the whole batch)
     solve_shared_backward(H, A, sol, gx) -> qpb_solve_shared_backward (a shared operand's gradient summed over the batch)
     solve_box_backward(H, sol, gx) -> qpb_solve_box_backward (gradients of a box solve, n <= 32)
+    solve_box_shared(H, f, lb, ub) -> qpb_solve_box_shared (a box solve with ONE H (n, n) for the whole batch, n <= 128)
+    solve_box_shared_backward(H, sol, gx) -> qpb_solve_box_shared_backward (its gradients, gH (n, n) summed over the batch, n <= 32)
     solve_range(H, f, A, bl, bu, meq) -> qpb_solve_range (two-sided rows bl <= A x <= bu, signed lam; n <= 32, m <= 64)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
@@ -122,6 +124,14 @@ _lib.qpb_solve_box_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_box_backward.restype = ctypes.c_int
 _lib.qpb_solve_box_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
 _lib.qpb_solve_box_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_box_shared.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
+_lib.qpb_solve_box_shared.restype = ctypes.c_int
+_lib.qpb_solve_box_shared_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
+_lib.qpb_solve_box_shared_host.restype = ctypes.c_int
+_lib.qpb_solve_box_shared_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
+_lib.qpb_solve_box_shared_backward.restype = ctypes.c_int
+_lib.qpb_solve_box_shared_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
+_lib.qpb_solve_box_shared_backward_host.restype = ctypes.c_int
 _lib.qpb_ref_solve.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 6
 _lib.qpb_ref_solve.restype = ctypes.c_int
 _lib.qpb_ref_solve_host.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 5
@@ -1018,6 +1028,125 @@ def solve_box_backward_host(H, sol: Solution, gx, *, need=BOX_NEED_ALL):
     rc = _lib.qpb_solve_box_backward_host(ctypes.byref(d), p(H), p(x), p(act), p(st), p(gx), p(gH), p(gf), p(glb),
                                           p(gub))
     _check(rc, "qpb_solve_box_backward_host")
+    return gH, gf, glb, gub
+
+
+def solve_box_shared(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0,
+                     out: Solution | None = None, stream=None) -> Solution:
+    """``solve_box`` with ONE H (n, n) for the whole batch (qpb_solve_box_shared,
+    n <= 128): H is read from one copy, no (B, n, n) tensor exists.  f (B,n),
+    lb / ub (B,n) or None as for ``solve_box``; the Solution is, bit for bit,
+    ``solve_box``'s on B copies of H.
+    """
+    import torch
+    if not (H.is_cuda and f.is_cuda):
+        raise ValueError("qpb.solve_box_shared expects CUDA (HIP) tensors; use solve_box_shared_host for numpy")
+    B, n = f.shape
+    for t in (H, f, lb, ub):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("inputs must be contiguous float64")
+        if t is not None and t.device != f.device:
+            raise ValueError("H, f, lb and ub must live on the same CUDA device")
+    if H.shape != (n, n) or any(t is not None and t.shape != (B, n) for t in (lb, ub)):
+        raise ValueError("shape mismatch: H must be (n, n), lb and ub (B, n)")
+    m = 2 * n
+    if out is None:
+        out = _empty_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_box_shared(ctypes.byref(d), _ptr(H), _ptr(f), _ptr(lb), _ptr(ub), _ptr(out.x),
+                                   _ptr(out.lam), _ptr(out.active), _ptr(out.status), _ptr(out.iters),
+                                   _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_shared")
+    return out
+
+
+def solve_box_shared_host(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0) -> Solution:
+    """numpy in / numpy out (qpb_solve_box_shared_host): ``solve_box_shared`` with host arrays."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    lb = None if lb is None else np.ascontiguousarray(lb, dtype=np.float64)
+    ub = None if ub is None else np.ascontiguousarray(ub, dtype=np.float64)
+    B, n = f.shape
+    if H.shape != (n, n) or any(t is not None and t.shape != (B, n) for t in (lb, ub)):
+        raise ValueError("shape mismatch: H must be (n, n), lb and ub (B, n)")
+    m = 2 * n
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, (m + 31) // 32), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_shared_host(ctypes.byref(d), p(H), p(f), p(lb), p(ub), p(x), p(lam), p(act), p(st), p(it))
+    _check(rc, "qpb_solve_box_shared_host")
+    return Solution(x, lam, act, st, it)
+
+
+def solve_box_shared_backward(H, sol: Solution, gx, *, need=BOX_NEED_ALL, stream=None):
+    """``solve_box_backward`` with ONE H (n, n) (qpb_solve_box_shared_backward):
+    given ``sol`` from ``solve_box_shared`` on (H, f, lb, ub) and the cotangent
+    ``gx`` (B, n), returns ``(gH, gf, glb, gub)``: gf, glb and gub (B, n) are
+    ``solve_box_backward``'s bit for bit, and gH is ONE (n, n) matrix, the sum
+    over the batch of the per-QP dl/dH, computed on the matrix cores without a
+    per-QP copy and without atomics (its bits depend on the inputs and on
+    (n, B) only).  QPs whose status is not OK contribute exactly 0.  ``need``
+    and ``sol.status`` as for ``solve_box_backward``.  n <= 32.
+    """
+    import torch
+    if not (H.is_cuda and gx.is_cuda):
+        raise ValueError("qpb.solve_box_shared_backward expects CUDA (HIP) tensors; "
+                         "use solve_box_shared_backward_host for numpy")
+    B, n = gx.shape
+    for t in (H, gx):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64")
+    if H.shape != (n, n):
+        raise ValueError("shape mismatch: H must be (n, n)")
+    need = _box_need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if (sol.active is None or not sol.active.is_cuda or not sol.active.is_contiguous()
+            or sol.active.shape != (B, (2 * n + 31) // 32) or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(2n/32)) CUDA tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(n, n) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    glb = new(B, n) if "lb" in need else None
+    gub = new(B, n) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_box_shared_backward(ctypes.byref(d), _ptr(H), _ptr(sol.x), _ptr(sol.active),
+                                            _ptr(sol.status), _ptr(gx), _ptr(gH), _ptr(gf), _ptr(glb), _ptr(gub),
+                                            _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_shared_backward")
+    return gH, gf, glb, gub
+
+
+def solve_box_shared_backward_host(H, sol: Solution, gx, *, need=BOX_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_box_shared_backward_host): ``solve_box_shared_backward`` with host arrays."""
+    import numpy as np
+    need = _box_need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    if H.shape != (n, n) or x.shape != (B, n) or act.shape != (B, (2 * n + 31) // 32):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros((n, n)) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    glb = np.zeros((B, n)) if "lb" in need else None
+    gub = np.zeros((B, n)) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_shared_backward_host(ctypes.byref(d), p(H), p(x), p(act), p(st), p(gx), p(gH), p(gf),
+                                                 p(glb), p(gub))
+    _check(rc, "qpb_solve_box_shared_backward_host")
     return gH, gf, glb, gub
 
 

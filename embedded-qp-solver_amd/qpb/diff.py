@@ -21,7 +21,10 @@ per-QP set-up is gone from both passes.  The gradients are bit for bit those of
 ``qpb.solve_shared_backward``; a forward without gradients pays nothing for them.
 
 ``solve_box(H, f, lb, ub)`` is ``qpb.solve_box`` with gradients for H, f, lb
-and ub (``qpb.solve_box_backward``, n <= 32).
+and ub (``qpb.solve_box_backward``, n <= 32).  A 2-D ``H`` (n, n) is ONE matrix
+for the whole batch there as well: the solve is ``qpb.solve_box_shared``, the
+backward ``qpb.solve_box_shared_backward``, ``H.grad`` is (n, n) -- the sum over
+the batch -- and no (B, n, n) tensor is allocated in either pass.
 
 ``solve_range(H, f, A, bl, bu, meq)`` is ``qpb.solve_range`` with gradients for
 H, f, A, bl and bu: the backward is ``qpb.solve_backward`` (or the shared one)
@@ -88,7 +91,9 @@ class BoxQPFunction(torch.autograd.Function):
         H, f = H.contiguous(), f.contiguous()
         lb = None if lb is None else lb.contiguous()
         ub = None if ub is None else ub.contiguous()
-        sol = qpb.solve_box(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.shared = H.dim() == 2  # one H for the batch
+        forward = qpb.solve_box_shared if ctx.shared else qpb.solve_box
+        sol = forward(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
         ctx.has = (True, True, lb is not None, ub is not None)
         ctx.save_for_backward(H, sol.x, sol.active, sol.status)
         ctx.mark_non_differentiable(sol.status)
@@ -103,7 +108,8 @@ class BoxQPFunction(torch.autograd.Function):
             return (None,) * 6
         sol = qpb.Solution(x, None, active, status, None)
         # on torch's current stream; above n = 32 this raises QPBError(ERR_UNSUPPORTED)
-        gH, gf, glb, gub = qpb.solve_box_backward(H, sol, gx.contiguous(), need=wanted)
+        backward = qpb.solve_box_shared_backward if ctx.shared else qpb.solve_box_backward
+        gH, gf, glb, gub = backward(H, sol, gx.contiguous(), need=wanted)
         return gH, gf, glb, gub, None, None
 
 
@@ -183,7 +189,11 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.
     contribute zero gradients.  The gradient is the derivative at fixed active
     set (qpb.h, qpb_solve_box_backward).  The forward solves every shape
     ``qpb.solve_box`` does (n <= 128); the backward needs n <= 32 and raises
-    ``QPBError(ERR_UNSUPPORTED)`` above that."""
+    ``QPBError(ERR_UNSUPPORTED)`` above that.  H may be 2-D, (n, n): one matrix
+    shared by the batch (``qpb.solve_box_shared``, with x bit for bit that of B
+    copies), whose gradient (n, n) is the sum over the batch
+    (``qpb.solve_box_shared_backward``), computed without a per-QP matrix; a
+    3-D H is the batched path unchanged."""
     return BoxQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol))
 
 

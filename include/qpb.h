@@ -15,6 +15,7 @@
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
+ *   ... a box solve with ONE H for the whole batch         qpb_solve_box_shared, qpb_solve_box_shared_backward
  *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
@@ -323,7 +324,7 @@ int qpb_solve_backward_host(const qpb_desc *desc, const double *H,
  * are looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
  * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
  * with m <= 64.  Follow-ups: the n <= 128 Gram class (qpb_gi_gram.hip) has no
- * shared form; a shared-H qpb_solve_box.  This call factors H per QP on purpose,
+ * shared form (a shared-H qpb_solve_box is qpb_solve_box_shared).  This call factors H per QP on purpose,
  * so that bit-for-bit equality with qpb_solve_eq is its test; factoring a
  * shared H ONCE is qpb_factor_shared and qpb_solve_factored below.
  * Device pointers; asynchronous on `stream`. */
@@ -766,6 +767,79 @@ int qpb_solve_box_backward_host(const qpb_desc *desc, const double *H,
 				const int32_t *status, const double *gx,
 				double *gH, double *gf, double *glb,
 				double *gub);
+
+/* qpb_solve_box with ONE H (n x n) for the whole batch, read from one copy (its
+ * QP stride is 0): an MPC loop's condensed Hessian with input bounds, or a QP
+ * layer's learned weight with a box.  f, lb, ub and every output are per QP in
+ * qpb_solve_box's layouts, at every shape it takes (n <= 128, m = 2n).
+ * Every output of every QP equals, bit for bit, what qpb_solve_box writes for
+ * that QP on B materialised copies of H: for every status of the contract
+ * above, and for NaN and +-Inf inputs as well (the kernels are qpb_solve_box's
+ * with another address: the SH forms of qpb_gi_box.hip and of the BOX kernels
+ * of qpb_gi_wave.hip and qpb_gi_gram.hip; H is factored per QP).  H is only
+ * read.  The flags select nothing, as there.
+ * Errors, in order, are qpb_solve_box's: the descriptor; m != 2n
+ * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
+ * missing H, f, x, lam, active or status QPB_ERR_INVALID_ARG (lb, ub and iters
+ * may be NULL); a missing device last.
+ * Follow-ups: factoring the shared H ONCE for box solves, so that L and L^-T
+ * are the same numbers for every QP (this call factors H per QP on purpose:
+ * bit-for-bit equality with qpb_solve_box is its test); general rows beside a
+ * box.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_box_shared(const qpb_desc *desc, const double *H, const double *f,
+			 const double *lb, const double *ub, double *x,
+			 double *lam, uint32_t *active, int32_t *status,
+			 int32_t *iters, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (H is one matrix). */
+int qpb_solve_box_shared_host(const qpb_desc *desc, const double *H,
+			      const double *f, const double *lb,
+			      const double *ub, double *x, double *lam,
+			      uint32_t *active, int32_t *status, int32_t *iters);
+
+/* qpb_solve_box_backward with ONE H (n x n): the gradient of the shared H is
+ * ONE matrix, the sum over the batch.
+ *   gf, glb, gub (B x n)   qpb_solve_box_backward's, bit for bit.
+ *   gH (n x n)             1/2 sum_k (dx_k x_k^T + x_k dx_k^T), symmetric bit
+ *                          for bit.
+ * A QP whose status is not QPB_OK contributes exactly 0 to the sum, even where
+ * its x holds NaN.  Each output may be NULL, at least one must be given; status
+ * may be NULL (every QP then counts as QPB_OK).  The rules of
+ * qpb_solve_box_backward at fixed active set (weakly active, both bits set,
+ * bits >= 2n) hold unchanged.
+ * Two passes, as in qpb_solve_shared_backward.  Pass 1 is the SH forms of
+ * qpb_kkt_bwd_box.hip launched without gH -- the factorisation of H masked by
+ * each QP's fixed variables differs per QP and stays per QP -- with dx going to
+ * gf or, when gf is NULL, to the workspace.  Pass 2 is that call's batch sum on
+ * the fp64 matrix cores (qpb_kkt_bwd_sum.hip), unchanged, with m = 0: once on
+ * the whole batch, also when pass 1 walks it in chunks.
+ *   workspace       sum_plan(B).slots * sum_slot_doubles(n, 0) doubles
+ *                   (csrc/qpb_route.h), plus B n when gf is NULL; cached per
+ *                   stream like every workspace.  gH NULL: no pass 2 and no
+ *                   workspace.
+ *   reproducible    no atomics: the bits of gH depend on the inputs and on
+ *                   (n, batch) only, whatever the stream, the workspace's
+ *                   history or the device.
+ * Errors, in order, are qpb_solve_box_backward's: the descriptor (m != 2n
+ * QPB_ERR_INVALID_ARG); flags != 0 QPB_ERR_INVALID_ARG; n > 32
+ * QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are looked at;
+ * missing pointers QPB_ERR_INVALID_ARG (H, x, active and gx; at least one
+ * output); a missing device last.
+ * Follow-ups: the box backward above n = 32; a factored box backward.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_box_shared_backward(const qpb_desc *desc, const double *H,
+				  const double *x, const uint32_t *active,
+				  const int32_t *status, const double *gx,
+				  double *gH, double *gf, double *glb,
+				  double *gub, void *stream);
+
+/* Same with host pointers (H and gH are one matrix each). */
+int qpb_solve_box_shared_backward_host(const qpb_desc *desc, const double *H,
+				       const double *x, const uint32_t *active,
+				       const int32_t *status, const double *gx,
+				       double *gH, double *gf, double *glb,
+				       double *gub);
 
 /* Reference-semantics solvers (qp_solvers.c replicas). */
 typedef enum qpb_ref_mode {
