@@ -440,6 +440,84 @@ extern "C" int qpb_solve_box_shared(const qpb_desc *d, const double *H, const do
       qpb::required(active, (m + 31) / 32), qpb::required(status, 1), qpb::optional(iters, 1));
 }
 
+// ---- that one H factored once -----------------------------------------------------
+extern "C" int64_t qpb_factor_box_doubles(int32_t n) {
+  if (n < 1) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_box_doubles: n must be >= 1");
+  if (qpb::route_box_factored(n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_factor_box_doubles: n=%d outside the factored box kernels (n<=%d)", n,
+                qpb::kBoxFactoredMaxN);
+  return qpb::bxfct::layout(n).size;
+}
+
+// the rules of qpb_factor_box up to the alignment and the device
+static int check_factor_box(int32_t n, const double *H, const double *bxfac) {
+  if (n < 1) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_box: n must be >= 1");
+  if (qpb::route_box_factored(n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_factor_box: n=%d outside the factored box kernels (n<=%d)", n,
+                qpb::kBoxFactoredMaxN);
+  if (!H || !bxfac) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_box: H and bxfac are required");
+  return 0;
+}
+
+extern "C" int qpb_factor_box(int32_t n, const double *H, double *bxfac, int32_t *fstatus, void *stream) {
+  int rc = check_factor_box(n, H, bxfac);
+  if (rc) return rc;
+  if ((uintptr_t)bxfac & 15) return fail(QPB_ERR_INVALID_ARG, "qpb_factor_box: bxfac must be 16-byte aligned");
+  rc = check_device();
+  if (rc) return rc;
+  qpb_gi_box_factor_launcher *const fn = qpb::route_box_factored(n).kernel == qpb::Kernel::gi_box
+                                             ? qpb_launch_gi_box_factor
+                                             : qpb_launch_gi_wave_box_factor;
+  const hipError_t e = fn(n, H, bxfac, fstatus, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(e, "qpb_factor_box launch");
+}
+
+// qpb_solve_box_factored's argument rules, in its order, up to the alignment and the device
+static int check_box_factored(const qpb_desc *d, const double *bxfac, const double *f, const double *x,
+                              const double *lam, const uint32_t *active, const int32_t *status, bool *empty) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  if (d->m != 2 * d->n)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_factored: m must be 2n (got n=%d m=%d)", d->n, d->m);
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_factored: flags must be 0 (got %d)", d->flags);
+  if (qpb::route_box_factored(d->n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_solve_box_factored: n=%d outside the factored box kernels (n<=%d)", d->n,
+                qpb::kBoxFactoredMaxN);
+  *empty = d->batch == 0;
+  if (*empty) return 0;
+  if (!bxfac || !f || !x || !lam || !active || !status)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_factored: bxfac, f, x, lam, active and status are required");
+  return 0;
+}
+
+extern "C" int qpb_solve_box_factored(const qpb_desc *d, const double *bxfac, const double *f, const double *lb,
+                                      const double *ub, double *x, double *lam, uint32_t *active, int32_t *status,
+                                      int32_t *iters, void *stream) {
+  bool empty = false;
+  int rc = check_box_factored(d, bxfac, f, x, lam, active, status, &empty);
+  if (rc || empty) return rc;
+  if ((uintptr_t)bxfac & 15)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_box_factored: bxfac must be 16-byte aligned");
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_box_factored(d->n);
+  qpb_gi_box_factored_launcher *const fn =
+      r.kernel == qpb::Kernel::gi_box ? qpb_launch_gi_box_factored : qpb_launch_gi_wave_box_factored;
+  const long long n = d->n, m = d->m;
+  // the chunk walk of the shared form: the buffer's QP stride is 0
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *fc, const double *lbc, const double *ubc, double *xc, double *lc,
+          uint32_t *ac, int32_t *sc, int32_t *ic) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e = fn(&c, bxfac, fc, lbc, ubc, xc, lc, ac, sc, ic, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_box_factored launch");
+      },
+      qpb::required(f, n), qpb::optional(lb, n), qpb::optional(ub, n), qpb::required(x, n), qpb::required(lam, m),
+      qpb::required(active, (m + 31) / 32), qpb::required(status, 1), qpb::optional(iters, 1));
+}
+
 extern "C" int qpb_solve_box_shared_backward(const qpb_desc *d, const double *H, const double *x,
                                              const uint32_t *active, const int32_t *status, const double *gx,
                                              double *gH, double *gf, double *glb, double *gub, void *stream) {
@@ -1244,6 +1322,55 @@ extern "C" int qpb_solve_box_shared_host(const qpb_desc *d, const double *H, con
   return 0;
 }
 
+extern "C" int qpb_factor_box_host(int32_t n, const double *H, double *bxfac, int32_t *fstatus) {
+  int rc = check_factor_box(n, H, bxfac);  // host pointers: the same rules (no alignment: the call's own buffer is loaded)
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t N = n, doubles = (size_t)qpb::bxfct::layout(n).size;
+  DevBuf dH, dF, dS;
+  HIPCHK(up(dH, H, N * N * 8), "H");
+  HIPCHK(alloc(dF, bxfac, doubles * 8), "bxfac");
+  HIPCHK(alloc(dS, fstatus, 4), "fstatus");
+  rc = qpb_factor_box(n, (double *)dH.p, (double *)dF.p, (int32_t *)dS.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_factor_box_host kernel");
+  HIPCHK(down(bxfac, dF, doubles * 8), "bxfac D2H");
+  HIPCHK(down(fstatus, dS, 4), "fstatus D2H");
+  return 0;
+}
+
+extern "C" int qpb_solve_box_factored_host(const qpb_desc *d, const double *bxfac, const double *f, const double *lb,
+                                           const double *ub, double *x, double *lam, uint32_t *active,
+                                           int32_t *status, int32_t *iters) {
+  bool empty = false;
+  int rc = check_box_factored(d, bxfac, f, x, lam, active, status, &empty);  // host pointers: the same rules
+  if (rc || empty) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
+  DevBuf dF, df, dlb, dub, dx, dl, da, ds, di;
+  HIPCHK(up(dF, bxfac, (size_t)qpb::bxfct::layout(d->n).size * 8), "bxfac");
+  HIPCHK(up(df, f, B * n * 8), "f");
+  HIPCHK(up(dlb, lb, B * n * 8), "lb");
+  HIPCHK(up(dub, ub, B * n * 8), "ub");
+  HIPCHK(alloc(dx, x, B * n * 8), "x");
+  HIPCHK(alloc(dl, lam, B * m * 8), "lam");
+  HIPCHK(alloc(da, active, B * w * 4), "active");
+  HIPCHK(alloc(ds, status, B * 4), "status");
+  HIPCHK(alloc(di, iters, B * 4), "iters");
+  rc = qpb_solve_box_factored(d, (double *)dF.p, (double *)df.p, (double *)dlb.p, (double *)dub.p, (double *)dx.p,
+                              (double *)dl.p, (uint32_t *)da.p, (int32_t *)ds.p, (int32_t *)di.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_box_factored_host kernel");
+  HIPCHK(down(x, dx, B * n * 8), "x D2H");
+  HIPCHK(down(lam, dl, B * m * 8), "lam D2H");
+  HIPCHK(down(active, da, B * w * 4), "active D2H");
+  HIPCHK(down(status, ds, B * 4), "status D2H");
+  HIPCHK(down(iters, di, B * 4), "iters D2H");
+  return 0;
+}
+
 extern "C" int qpb_solve_box_shared_backward_host(const qpb_desc *d, const double *H, const double *x,
                                                   const uint32_t *active, const int32_t *status, const double *gx,
                                                   double *gH, double *gf, double *glb, double *gub) {
@@ -1420,4 +1547,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed; kkt_bwd_fact v1.0: qpb_solve_factored_backward for n <= 32 and m <= 64, a shared H and A factored once by the backward kernels' own set-up into a buffer of the backward's own that holds L, 1 / L_kk, D = A L^-T and the sweep's multipliers, the factored forms of kkt_bwd take u from them by the set-up's own operations, outputs bit for bit those of qpb_solve_shared_backward; box_shared v1.0: qpb_solve_box_shared for n <= 128 and qpb_solve_box_shared_backward for n <= 32, one H for a batch of box QPs read from one copy through a run-time QP stride in the SH forms of gi_box, gi_wave's and gi_gram's BOX kernels and kkt_bwd_box, outputs bit for bit those of qpb_solve_box and qpb_solve_box_backward on copies, gH summed over the batch by kkt_bwd_sum at m = 0)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed; kkt_bwd_fact v1.0: qpb_solve_factored_backward for n <= 32 and m <= 64, a shared H and A factored once by the backward kernels' own set-up into a buffer of the backward's own that holds L, 1 / L_kk, D = A L^-T and the sweep's multipliers, the factored forms of kkt_bwd take u from them by the set-up's own operations, outputs bit for bit those of qpb_solve_shared_backward; box_shared v1.0: qpb_solve_box_shared for n <= 128 and qpb_solve_box_shared_backward for n <= 32, one H for a batch of box QPs read from one copy through a run-time QP stride in the SH forms of gi_box, gi_wave's and gi_gram's BOX kernels and kkt_bwd_box, outputs bit for bit those of qpb_solve_box and qpb_solve_box_backward on copies, gH summed over the batch by kkt_bwd_sum at m = 0; box_fact v1.0: qpb_factor_box and qpb_solve_box_factored for n <= 32, the one H of a batch of box QPs factored once by the class's own load and sweep into a buffer that holds L, the rows of L^-T and their squared norms in the order the solve's lanes load them and neither H nor A, the factored forms of gi_box and of gi_wave's BOX kernel start from a forward substitution for y = L^-1 f with e = L^-T y accumulated alongside and the slacks ub + e and -lb - e in place of the set-up sweep, the lower bounds' rows negated as they are loaded)"; }

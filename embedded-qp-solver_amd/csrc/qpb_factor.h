@@ -137,4 +137,64 @@ static_assert(layout(32, 64).L % 2 == 0 && layout(32, 64).ik % 2 == 0 && layout(
 static_assert(kDenseL % 32 == 0 && kDenseL >= 16 * 17 / 2 && kWaveL % 2 == 0);
 
 }  // namespace bfct
+
+// The box solve's buffer (qpb_factor_box -> qpb_solve_box_factored), a third
+// layout: A = [I; -I] is implicit, so D = [L^-T; -L^-T] is stored once, as the
+// rows of L^-T, and the box recovery x = -H^-1 (f + lam_u - lam_l) reads
+// neither H nor A -- the buffer holds neither.  It belongs to one n; the class
+// follows from n alone, as qpb_solve_box's does.  Offsets in doubles.
+//
+//   header (kHdr)   [0] 0 or QPB_NOT_SPD, as a double; [1] n; [2] 16 or 32, the
+//                   padded n of the class
+//   n <= 16 (gi_box: lane l of a QP's 16 holds row l of L and row l of L^-T):
+//     L    [t][l][c], t < 8, c < 2: L[l][2t + c] -- one 16-byte load per lane and
+//          t, the 16 lanes read 256 contiguous bytes; 16 x 16, the identity
+//          outside n, zero right of the diagonal
+//     D    [t][l][c]: row l of L^-T, entry 2t + c (the lower bound's row is its
+//          negative)
+//     dn2  [l]: |row l|^2, what the unfactored kernel starts fn2 from
+//   16 < n <= 32 (gi_wave's BOX form: lane l < n holds row l of L^-T, lane n + i
+//   its negated row i):
+//     L    packed rows, L[i][j] at i (i + 1) / 2 + j, 32 rows (zero from row n
+//          on): copied flat into the kernel's LDS, element i 64 + l by lane l
+//     D    [t][r][c], t < 16, r < 32, c < 2: row r of L^-T, entry 2t + c, zero
+//          from row n on -- a lane's load is 16 bytes, lanes 0 .. n-1 and
+//          n .. 2n-1 each read consecutive addresses
+//     dn2  [r]: |row r|^2, what the unfactored kernel starts dn from; zero from
+//          row n on
+namespace bxfct {
+
+constexpr int kHdr = fct::kHdr;
+constexpr int kMaxN = 32;  // the limit of qpb_factor_box and qpb_solve_box_factored
+
+struct Layout {
+  bool box16;            // the n <= 16 class
+  int np;                // the padded n: 16 or 32
+  long long L, D, dn2;   // offsets
+  long long size;        // doubles in all
+};
+
+constexpr Layout layout(int n) {
+  Layout y{};
+  y.box16 = n <= 16;
+  y.np = y.box16 ? 16 : 32;
+  y.L = kHdr;
+  y.D = y.L + (y.box16 ? 256 : 32 * 33 / 2);
+  y.dn2 = y.D + (long long)y.np * y.np;
+  y.size = y.dn2 + y.np;
+  return y;
+}
+
+static_assert(layout(1).box16 && layout(16).box16 && !layout(17).box16 && !layout(32).box16);
+static_assert(layout(1).size == 8 + 256 + 256 + 16 && layout(16).size == layout(1).size);
+static_assert(layout(17).size == 8 + 528 + 1024 + 32 && layout(32).size == layout(17).size);
+// the class boundary is the general buffer's at m = 2n
+static_assert(layout(16).box16 == fct::layout(16, 32).dense && layout(17).box16 == fct::layout(17, 34).dense);
+// every section starts on a 16-byte boundary (the b128 loads of L and D), and so does the end
+static_assert(layout(16).L % 2 == 0 && layout(16).D % 2 == 0 && layout(16).dn2 % 2 == 0 && layout(16).size % 2 == 0);
+static_assert(layout(32).L % 2 == 0 && layout(32).D % 2 == 0 && layout(32).dn2 % 2 == 0 && layout(32).size % 2 == 0);
+// no H and no A: smaller than the general buffer of the explicit A = [I; -I]
+static_assert(layout(16).size < fct::layout(16, 32).size && layout(32).size < fct::layout(32, 64).size);
+
+}  // namespace bxfct
 }  // namespace qpb

@@ -22,6 +22,9 @@
 // (or a NULL lb / ub) are absent constraints: their slack is +inf.
 // The QP's LDS slot (L | R, its column 0 the exchange row | s_p) and the steps
 // the kernel has in common with gi_dense are qpb_row16.h's.
+#include <type_traits>
+
+#include "qpb_factor.h"  // the box factor buffer of qpb_factor_box / qpb_solve_box_factored
 #include "qpb_launch.h"  // with qpb.h
 #include "qpb_row16.h"
 
@@ -39,6 +42,23 @@ using namespace row16;
 // rows per instruction), so the outputs are the other form's bit for bit.
 // Without SH the pack is empty, and the signature and the code object stay as
 // they were.
+// The factor forms (qpb_factor.h, bxfct, has the buffer) ride in the same pack:
+// BoxFactorOut (qpb_factor_box): ONE problem (batch 1, no f and no bounds), the
+// kernel's own load and sweep, then L, the lane's row of L^-T, its squared norm
+// and what the sweep found go to the buffer, and nothing else runs.
+// BoxFactorIn (qpb_solve_box_factored): no H is loaded and nothing is swept --
+// the lane's rows of L and of L^-T come from the buffer with 16-byte loads at
+// consecutive addresses, fn2 from the stored squared norm; y = L^-1 f is a
+// lane-parallel forward substitution whose steps also accumulate e = (L^-T y)_l
+// (both by DPP-fused FMAs that read y_k from lane k), and the slacks are
+// ub + e and -lb - e.  From the active-set loop on the code is the other forms'.
+struct BoxFactorOut {
+  double *fac;
+  int32_t *fstatus;  // may be NULL
+};
+struct BoxFactorIn {
+  const double *fac;
+};
 template <bool N16, bool SH = false, class... STR>
 __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict__ Hg, const double *__restrict__ fg,
                                                        const double *__restrict__ lbg, const double *__restrict__ ubg,
@@ -46,8 +66,10 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
                                                        uint32_t *__restrict__ actg, int32_t *__restrict__ statg,
                                                        int32_t *__restrict__ itg, int n, long long batch,
                                                        int max_iter, double feas_tol, STR... strideH) {
-  static_assert(sizeof...(STR) == (SH ? 1 : 0) && (std::is_same_v<STR, long long> && ...),
-                "the shared form alone takes the stride");
+  constexpr bool FO = (std::is_same_v<STR, BoxFactorOut> || ...), FI = (std::is_same_v<STR, BoxFactorIn> || ...);
+  static_assert(sizeof...(STR) == ((SH || FO || FI) ? 1 : 0) && (FO || FI || (std::is_same_v<STR, long long> && ...)) &&
+                    !(SH && (FO || FI)),
+                "the shared form alone takes the stride, a factor form its buffer");
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -62,17 +84,42 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   // ------------------------------------------------------------------ load
   const bool var = N16 || l < n;  // lane l carries variable l
   const int lc = var ? l : n - 1;
-  const double *Hq;
+  [[maybe_unused]] const double *Hq;
   if constexpr (SH)
     Hq = Hg + g * (strideH + ...);
   else
     Hq = Hg + g * (long long)n * n;
-  const double fv = fg[g * n + lc];
+  double fv0 = 0.0;
+  if constexpr (!FO) fv0 = fg[g * n + lc];  // the factor kernel has no f
+  const double fv = fv0;
   const double ubv = ubg ? ubg[g * n + lc] : kInf;
   const double lbv = lbg ? lbg[g * n + lc] : -kInf;
   double Lr[NL];  // row l of H, becomes row l of L
   double E[NL];   // row l of D = L^{-T}, from e_l
-  if constexpr (N16) {
+  [[maybe_unused]] double fdn = 0.0;  // FI: |row l of L^-T|^2 from the buffer
+  [[maybe_unused]] bool fspd = true;  // FI: the buffer's H was positive definite
+  constexpr int oFL = bxfct::kHdr, oFD = oFL + NL * NL, oFN = oFD + NL * NL;
+  static_assert(bxfct::layout(NL).L == oFL && bxfct::layout(1).D == oFD && bxfct::layout(NL).dn2 == oFN &&
+                bxfct::layout(1).size == oFN + NL && bxfct::layout(NL).np == NL);
+  if constexpr (FI) {
+    // the buffer in place of H: 16 bytes per lane at consecutive addresses,
+    // the same for the wave's four QPs and every other wave
+    const double *facg = [](BoxFactorIn a) { return a; }(strideH...).fac;
+    fspd = facg[0] != (double)QPB_NOT_SPD;
+#pragma unroll
+    for (int t = 0; t < NL / 2; ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&facg[oFL + (t * NL + l) * 2]);
+      Lr[2 * t] = v.x;
+      Lr[2 * t + 1] = v.y;
+    }
+#pragma unroll
+    for (int t = 0; t < NL / 2; ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&facg[oFD + (t * NL + l) * 2]);
+      E[2 * t] = v.x;
+      E[2 * t + 1] = v.y;
+    }
+    fdn = facg[oFN + l];
+  } else if constexpr (N16) {
     // one instruction reads two whole rows of each of the wave's 4 QPs; the
     // rows reach their owner lanes through a transpose in this QP's LDS slot
     // (L and R are written after the factorisation)
@@ -93,8 +140,10 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
 #pragma unroll
     for (int j = 0; j < NL; ++j) Lr[j] = h_padded(Hq, l, lc, n, j);
   }
+  if constexpr (!FI) {
 #pragma unroll
-  for (int j = 0; j < NL; ++j) E[j] = l == j ? 1.0 : 0.0;
+    for (int j = 0; j < NL; ++j) E[j] = l == j ? 1.0 : 0.0;
+  }
   // b of the two rows: ub (x_l <= ub_l) and -lb (-x_l <= -lb_l)
   const double bu = var ? ubv : kInf, bl = var ? -lbv : kInf;
   // violation thresholds of the (unit-norm) rows; -inf for an absent bound
@@ -106,7 +155,28 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
   // alongside (y_k is final at step k)
   bool spd = true;
   double ya = fl, ey = 0.0;
-  unroll<NL>([&](auto K) {
+  if constexpr (FI) {
+    // ---- y = L^{-1} f and e = (L^{-T} y)_l from the stored L and L^{-T}, on the
+    // negated accumulator na = -(f - sum L y): step k forms t = na ninv, which is
+    // y_k on lane k (ninv = -1 / L[l][l]), and both FMAs of the step read it from
+    // lane k by their own DPP broadcast.  t is a VALU result read through DPP:
+    // dpp_ready issues the wait states.  Lane k's own na becomes 0 at step k and
+    // is dead from there on, like the entries of its row of L right of the
+    // diagonal (zero in the buffer).
+    spd = fspd;
+    store_l(Lp, l, Lr);  // for the final solves
+    const double ninv = -rcp1(Lp[lrow(l) + l]);
+    wave_lds_sync();
+    double na = -ya;
+    unroll<NL>([&](auto K) {
+      constexpr int k = K;
+      const double t = na * ninv;
+      dpp_ready(t);
+      fmac_bc<k>(ey, t, E[k]);
+      fmac_bc<k>(na, t, Lr[k]);
+    });
+  }
+  if constexpr (!FI) unroll<NL>([&](auto K) {
     constexpr int k = K;
     __builtin_amdgcn_sched_barrier(0);
     const double akk = bc<k>(Lr[k]);
@@ -128,13 +198,36 @@ __global__ __launch_bounds__(64, 3) void gi_box_kernel(const double *__restrict_
     ya = __builtin_fma(-c, fk, ya);
     ey = __builtin_fma(E[k], fk * ik, ey);
   });
-  __builtin_amdgcn_sched_barrier(0);
-  store_l(Lp, l, Lr);  // for the final solves
+  if constexpr (!FI) {
+    __builtin_amdgcn_sched_barrier(0);
+    store_l(Lp, l, Lr);  // for the final solves
+  }
   // slacks of the unconstrained minimiser x0 = -L^{-T} y: b + D y per row
   double su = bu + ey, sl = bl - ey;
   // |D[l, q:]|^2, the free part of both of the lane's rows (scale of the
   // selection key, as qpb_gi.hip)
-  float fn2 = (float)dot2<NL>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
+  double dn2;
+  if constexpr (FI) dn2 = fdn;
+  else dn2 = dot2<NL>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
+  if constexpr (FO) {
+    // ---- the factor kernel ends here: the live row (QP 0) writes the buffer
+    const BoxFactorOut fo = [](BoxFactorOut a) { return a; }(strideH...);
+    const int found = spd ? QPB_OK : QPB_NOT_SPD;
+    if (live) {
+      double *fac = fo.fac;
+      if (l < bxfct::kHdr) fac[l] = l == 0 ? (double)found : l == 1 ? (double)n : l == 2 ? (double)NL : 0.0;
+      if (l == 0 && fo.fstatus) fo.fstatus[0] = found;
+#pragma unroll
+      for (int t = 0; t < NL / 2; ++t) {  // zero right of the diagonal (the sweep leaves dead values there)
+        *reinterpret_cast<double2 *>(&fac[oFL + (t * NL + l) * 2]) =
+            make_double2(2 * t <= l ? Lr[2 * t] : 0.0, 2 * t + 1 <= l ? Lr[2 * t + 1] : 0.0);
+        *reinterpret_cast<double2 *>(&fac[oFD + (t * NL + l) * 2]) = make_double2(E[2 * t], E[2 * t + 1]);
+      }
+      fac[oFN + l] = dn2;
+    }
+    return;
+  }
+  float fn2 = (float)dn2;
 
   // ------------------------------------------------------ active-set loop
   // zeroed in pairs at lane-rotated positions (the same position in every
@@ -421,5 +514,31 @@ extern "C" hipError_t qpb_launch_gi_box_shared(const qpb_desc *d, const double *
                                  : qpb::box::gi_box_kernel<false, true, long long>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, H, f, lb, ub, x, lam, active, status,
                      iters, d->n, (long long)d->batch, max_iter, tol, strideH);
+  return hipGetLastError();
+}
+
+// qpb_factor_box for n <= 16: one launch of one wavefront, its first QP's lanes write the buffer
+extern "C" hipError_t qpb_launch_gi_box_factor(int n, const double *H, double *bxfac, int32_t *fstatus,
+                                               hipStream_t stream) {
+  using qpb::box::BoxFactorOut;
+  const auto kernel = n == 16 ? qpb::box::gi_box_kernel<true, false, BoxFactorOut>
+                              : qpb::box::gi_box_kernel<false, false, BoxFactorOut>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, stream, H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, n, 1LL, 0, 0.0, BoxFactorOut{bxfac, fstatus});
+  return hipGetLastError();
+}
+
+// qpb_solve_box_factored for n <= 16: the factored forms on such a buffer
+extern "C" hipError_t qpb_launch_gi_box_factored(const qpb_desc *d, const double *bxfac, const double *f,
+                                                 const double *lb, const double *ub, double *x, double *lam,
+                                                 uint32_t *active, int32_t *status, int32_t *iters,
+                                                 hipStream_t stream) {
+  using qpb::box::BoxFactorIn;
+  const long long blocks = (d->batch + qpb::box::QPB - 1) / qpb::box::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const auto kernel = d->n == 16 ? qpb::box::gi_box_kernel<true, false, BoxFactorIn>
+                                 : qpb::box::gi_box_kernel<false, false, BoxFactorIn>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, bxfac, f, lb, ub, x, lam, active, status,
+                     iters, d->n, (long long)d->batch, max_iter, tol, BoxFactorIn{bxfac});
   return hipGetLastError();
 }

@@ -121,6 +121,11 @@ struct RangeArgs {
 // stored |a_r| and dn from the stored |D_r|^2; y = L^-1 f is the lane-parallel
 // forward substitution of the finish, and s = b + D y the line the sweep ends
 // with.  From there on the code is the other forms'.
+// BOX with FactorOut / FactorIn (qpb_factor_box, qpb_solve_box_factored): the
+// same two forms on the box buffer (qpb_factor.h, bxfct), which holds the rows of
+// L^-T once -- lane l < n loads row l, lane n + i the negated row i, what the
+// sweep turns +-e into -- and neither H nor A; the rows' norms before the sweep
+// are 1, so the thresholds are the unfactored BOX form's bit for bit.
 struct FactorOut {
   double *fac;
   int32_t *fstatus;  // may be NULL
@@ -150,8 +155,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...) || RF;
   constexpr bool FO = (std::is_same_v<RGA, FactorOut> || ...), FI = (std::is_same_v<RGA, FactorIn> || ...) || RF;
   static_assert(sizeof...(RGA) <= 1 && (sizeof...(RGA) == 0 || RG || FO || FI), "one trailing argument at most");
-  static_assert(!(FO || FI) || (!(STAMP || REDO || BOX || SH) && (!FO || !EQ)),
-                "the factor forms are the plain or the EQ kernel's");
+  static_assert(!(FO || FI) || (!(STAMP || REDO || SH) && (!FO || !EQ)),
+                "the factor forms are the plain, the EQ or the BOX kernel's");
   static_assert(!EQ || !(STAMP || REDO || BOX), "the EQ form is the plain kernel's");
   static_assert(!SH || !(STAMP || REDO), "the shared form is the plain, the EQ or the BOX kernel's");
   static_assert(!RG || (EQ && SH != RF && sizeof...(RGA) == 1),
@@ -200,8 +205,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // BOX: Ag = lb, bg = ub (n per QP, either may be NULL), m = 2n; Aq and bq
   // alias Hq (BOX + SH, qpb_solve_box_shared: only QPB_SHARED_H means anything,
   // and the bounds stay per QP -- they are read through Ag and bg at g)
-  const double *Aq = FI       ? facg + fct::layout(n, m).A
-                     : BOX    ? Hq
+  const double *Aq = BOX      ? Hq
+                     : FI     ? facg + fct::layout(n, m).A
                      : m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n)
                              : Hq;
   const double *bq = BOX ? Hq : m > 0 ? bg + g * (long long)m : Hq;
@@ -243,7 +248,31 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   [[maybe_unused]] bool fspd = true;
   constexpr int oFL = fct::kHdr, oFD = oFL + L_SIZE, oFN = oFD + 64 * NP, oFA = oFN + 3 * 64;
   static_assert(fct::layout(NP, 64).D == oFD && fct::layout(NP, 64).an2 == oFN && fct::layout(17, 0).A == oFA);
-  if constexpr (FI) {
+  // the box buffer: L, the 32 rows of L^-T, their squared norms
+  constexpr int oBL = bxfct::kHdr, oBD = oBL + L_SIZE, oBN = oBD + NP * NP;
+  static_assert(bxfct::layout(NP).L == oBL && bxfct::layout(17).D == oBD && bxfct::layout(NP).dn2 == oBN &&
+                bxfct::layout(17).size == oBN + NP && bxfct::layout(NP).np == NP);
+  if constexpr (FI && BOX) {
+    fspd = facg[0] != (double)QPB_NOT_SPD;
+#pragma unroll
+    for (int i = 0; i < (L_SIZE + 63) / 64; ++i) {
+      const int e = i * 64 + l;
+      if (e < L_SIZE) Lp[e] = facg[oBL + e];
+    }
+    // row l of D: row l of L^-T (l < n), minus row l - n (n <= l < 2n), or a
+    // zero row (the buffer's row 31 where n < 32; at n = 32 every lane has one)
+    const bool lowr = l >= n && l < 2 * n;
+    const int ri = l < n ? l : lowr ? l - n : NP - 1;
+#pragma unroll
+    for (int t = 0; t < NH; ++t) {
+      const double2 v = *reinterpret_cast<const double2 *>(&facg[oBD + (t * NP + ri) * 2]);
+      E[2 * t] = lowr ? -v.x : v.x;
+      E[2 * t + 1] = lowr ? -v.y : v.y;
+    }
+    f_dn = facg[oBN + ri];
+    wave_lds_sync();
+  }
+  if constexpr (FI && !BOX) {
     fspd = facg[0] != (double)QPB_NOT_SPD;
 #pragma unroll
     for (int i = 0; i < (L_SIZE + 63) / 64; ++i) {
@@ -347,7 +376,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
 
   clk.tick(0);  // load
   double nrm2;
-  if constexpr (FI) nrm2 = f_an2;
+  if constexpr (FI && BOX) nrm2 = rowok ? 1.0 : 0.0;  // |+-e|^2, what the unfactored form sums
+  else if constexpr (FI) nrm2 = f_an2;
   else nrm2 = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
   [[maybe_unused]] double rg_b = 0.0, rg_thr = 0.0;
   [[maybe_unused]] bool rg_inf = false;
@@ -385,7 +415,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // violated: s / |D row| < -tol (1 + |b| / |D row|), i.e. s < -tol (|D row| + |b|)
   double thr;
   if constexpr (RG) thr = rg_thr;
-  else if constexpr (FI) thr = (rowok && nrm2 > 0.0) ? -feas_tol * (f_an + __builtin_fabs(bl)) : -kInf;
+  else if constexpr (FI && !BOX) thr = (rowok && nrm2 > 0.0) ? -feas_tol * (f_an + __builtin_fabs(bl)) : -kInf;
   else thr = (rowok && nrm2 > 0.0) ? -feas_tol * (nrm2 * rsq(nrm2) + __builtin_fabs(bl)) : -kInf;
   const bool infeasible0 =
       RG ? rg_inf : wave_any(rowok && nrm2 == 0.0 && bl < -feas_tol * (1.0 + __builtin_fabs(bl)));
@@ -510,7 +540,28 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   double dn;
   if constexpr (FI) dn = f_dn;
   else dn = dot2<NP>([&](int j) { return E[j]; }, [&](int j) { return E[j]; });
-  if constexpr (FO) {
+  if constexpr (FO && BOX) {
+    // ---- the box factor kernel ends here (one workgroup, g == 0): the buffer.
+    // Lanes 0 .. 31 write one row each, zeros from row n on (lanes n .. 2n-1
+    // hold the negated rows, which the solve forms itself)
+    const int found = spd ? QPB_OK : QPB_NOT_SPD;
+    if (l < bxfct::kHdr) faco[l] = l == 0 ? (double)found : l == 1 ? (double)n : l == 2 ? (double)NP : 0.0;
+    if (l == 0 && fstat) fstat[0] = found;
+#pragma unroll
+    for (int i = 0; i < (L_SIZE + 63) / 64; ++i) {
+      const int e = i * 64 + l;
+      if (e < L_SIZE) faco[oBL + e] = Lp[e];
+    }
+    if (l < NP) {
+#pragma unroll
+      for (int t = 0; t < NH; ++t)
+        *reinterpret_cast<double2 *>(&faco[oBD + (t * NP + l) * 2]) =
+            make_double2(l < n ? E[2 * t] : 0.0, l < n ? E[2 * t + 1] : 0.0);
+      faco[oBN + l] = l < n ? dn : 0.0;
+    }
+    return;
+  }
+  if constexpr (FO && !BOX) {
     // ---- the factor kernel ends here (one workgroup, g == 0): the buffer
     const int found = !spd ? QPB_NOT_SPD : nan0 ? QPB_NUMERICAL : QPB_OK;
     if (l < fct::kHdr)
@@ -1129,5 +1180,26 @@ extern "C" hipError_t qpb_launch_gi_wave_range_factored(const qpb_desc *d, int m
                      dim3((unsigned)d->batch), dim3(64), 0, stream, fac, f, fac, bu, x, lam, active, status, iters,
                      d->n, d->m | (meq << qpb::wv::kEqShift), (long long)d->batch, max_iter, tol, nullptr,
                      qpb::wv::RangeFactorIn{fac, bl, lower});
+  return hipGetLastError();
+}
+
+// qpb_factor_box for 16 < n <= 32: one launch of one wavefront, the BOX form's own load and sweep
+extern "C" hipError_t qpb_launch_gi_wave_box_factor(int n, const double *H, double *bxfac, int32_t *fstatus,
+                                                    hipStream_t stream) {
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, true, false, false, qpb::wv::FactorOut>), dim3(1),
+                     dim3(64), 0, stream, H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n,
+                     2 * n, 1LL, 0, 0.0, nullptr, qpb::wv::FactorOut{bxfac, fstatus});
+  return hipGetLastError();
+}
+
+// qpb_solve_box_factored for 16 < n <= 32: the BOX form on such a buffer
+extern "C" hipError_t qpb_launch_gi_wave_box_factored(const qpb_desc *d, const double *bxfac, const double *f,
+                                                      const double *lb, const double *ub, double *x, double *lam,
+                                                      uint32_t *active, int32_t *status, int32_t *iters,
+                                                      hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, true, false, false, qpb::wv::FactorIn>),
+                     dim3((unsigned)d->batch), dim3(64), 0, stream, bxfac, f, lb, ub, x, lam, active, status, iters,
+                     d->n, d->m, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::FactorIn{bxfac});
   return hipGetLastError();
 }

@@ -50,6 +50,20 @@ typedef hipError_t qpb_gi_box_shared_launcher(const qpb_desc *d, const double *H
 QPB_LAUNCHER qpb_gi_box_shared_launcher qpb_launch_gi_box_shared,  // n <= 16 (qpb_gi_box.hip)
     qpb_launch_gi_wave_box_shared,                                 // ... n <= 32 (qpb_gi_wave.hip)
     qpb_launch_gi_gram_box_shared;                                 // ... n <= 128 (qpb_gi_gram.hip)
+// qpb_factor_box: ONE H (n x n) into the class's box factor buffer (qpb_factor.h,
+// bxfct), one small launch of the class's own kernel in its factor form; fstatus
+// may be NULL
+typedef hipError_t qpb_gi_box_factor_launcher(int n, const double *H, double *bxfac, int32_t *fstatus,
+                                              hipStream_t stream);
+QPB_LAUNCHER qpb_gi_box_factor_launcher qpb_launch_gi_box_factor,  // n <= 16 (qpb_gi_box.hip)
+    qpb_launch_gi_wave_box_factor;                                 // ... n <= 32 (qpb_gi_wave.hip)
+// qpb_solve_box_factored: the box launchers on such a buffer in place of H
+typedef hipError_t qpb_gi_box_factored_launcher(const qpb_desc *d, const double *bxfac, const double *f,
+                                                const double *lb, const double *ub, double *x, double *lam,
+                                                uint32_t *active, int32_t *status, int32_t *iters,
+                                                hipStream_t stream);
+QPB_LAUNCHER qpb_gi_box_factored_launcher qpb_launch_gi_box_factored,  // n <= 16 (qpb_gi_box.hip)
+    qpb_launch_gi_wave_box_factored;                                   // ... n <= 32 (qpb_gi_wave.hip)
 // qpb_solve_box_shared_backward, pass 1: qpb_launch_kkt_bwd_box with that stride
 // (gH NULL: pass 2, qpb_launch_kkt_bwd_sum with m == 0, sums the gradient)
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box_shared(const qpb_desc *d, long long strideH, const double *H,

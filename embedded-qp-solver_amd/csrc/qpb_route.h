@@ -4,6 +4,7 @@
 #pragma once
 
 #include "qpb.h"  // QPB_FLAG_MIXED, QPB_FLAG_DIAG_WAVE
+#include "qpb_factor.h"  // bxfct: the box factor buffer's class boundary (host-compilable as well)
 
 namespace qpb {
 
@@ -147,6 +148,43 @@ static_assert(route_bwd_box_shared(16).kernel == route_bwd_box(16).kernel &&
               route_bwd_box_shared(32).kernel == route_bwd_box(32).kernel &&
               route_bwd_box_shared(32).step == route_bwd_box(32).step &&
               route_bwd_box_shared(kBwdBoxMaxN + 1).step == 0);
+
+// qpb_factor_box and qpb_solve_box_factored: qpb_solve_box's own two
+// wavefront-level classes, whose factor kernel writes and whose factored form
+// reads the class's own layout of the box buffer (qpb_factor.h, bxfct, decides
+// the class by the same limit); above them -- the Gram class, whose set-up runs
+// on the matrix cores -- there is neither yet: step 0, and the calls are
+// unsupported.
+constexpr Route route_box_factored(int n) {
+  if (n <= 16) return {Kernel::gi_box, step_of(Kernel::gi_box)};
+  if (n <= 32) return {Kernel::gi_wave_box, step_of(Kernel::gi_wave_box)};
+  return {Kernel::gi_gram_box, 0};
+}
+constexpr int kBoxFactoredMaxN = 32;  // the limit route_box_factored's step 0 stands for
+
+static_assert(route_box_factored(1).kernel == Kernel::gi_box && route_box_factored(16).kernel == Kernel::gi_box);
+static_assert(route_box_factored(17).kernel == Kernel::gi_wave_box &&
+              route_box_factored(32).kernel == Kernel::gi_wave_box);
+static_assert(route_box_factored(16).step == 1LL << 27 && route_box_factored(32).step == 1LL << 25);
+static_assert(route_box_factored(33).step == 0 && route_box_factored(128).step == 0);
+static_assert(route_box_factored(kBoxFactoredMaxN).step > 0 && route_box_factored(kBoxFactoredMaxN + 1).step == 0);
+// up to the limit it names qpb_solve_box's class and step
+static_assert(route_box_factored(1).kernel == route(1, 2, 0, true).kernel &&
+              route_box_factored(16).kernel == route(16, 32, 0, true).kernel &&
+              route_box_factored(16).step == route(16, 32, 0, true).step &&
+              route_box_factored(17).kernel == route(17, 34, 0, true).kernel &&
+              route_box_factored(32).kernel == route(32, 64, 0, true).kernel &&
+              route_box_factored(32).step == route(32, 64, 0, true).step);
+// the buffer's layout changes class where the route does, and ends where it does
+static_assert(bxfct::layout(1).box16 == (route_box_factored(1).kernel == Kernel::gi_box) &&
+              bxfct::layout(16).box16 == (route_box_factored(16).kernel == Kernel::gi_box) &&
+              bxfct::layout(17).box16 == (route_box_factored(17).kernel == Kernel::gi_box) &&
+              bxfct::layout(32).box16 == (route_box_factored(32).kernel == Kernel::gi_box) &&
+              bxfct::kMaxN == kBoxFactoredMaxN);
+// the outputs go to qpb_solve_box_shared_backward: the same classes and limit
+static_assert(route_box_factored(16).kernel == route_bwd_box_shared(16).kernel &&
+              route_box_factored(17).kernel == route_bwd_box_shared(17).kernel &&
+              kBoxFactoredMaxN == kBwdBoxMaxN);
 
 // qpb_solve_shared with a shared H or A (and any meq): route_eq, the SH forms
 // of the two wavefront-level classes; above them -- the Gram class -- there is

@@ -132,6 +132,16 @@ _lib.qpb_solve_box_shared_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 1
 _lib.qpb_solve_box_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_box_shared_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
 _lib.qpb_solve_box_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_factor_box_doubles.argtypes = [ctypes.c_int32]
+_lib.qpb_factor_box_doubles.restype = ctypes.c_int64
+_lib.qpb_factor_box.argtypes = [ctypes.c_int32] + [_vp] * 4
+_lib.qpb_factor_box.restype = ctypes.c_int
+_lib.qpb_factor_box_host.argtypes = [ctypes.c_int32] + [_vp] * 3
+_lib.qpb_factor_box_host.restype = ctypes.c_int
+_lib.qpb_solve_box_factored.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
+_lib.qpb_solve_box_factored.restype = ctypes.c_int
+_lib.qpb_solve_box_factored_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
+_lib.qpb_solve_box_factored_host.restype = ctypes.c_int
 _lib.qpb_ref_solve.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 6
 _lib.qpb_ref_solve.restype = ctypes.c_int
 _lib.qpb_ref_solve_host.argtypes = [ctypes.POINTER(RefDesc)] + [_vp] * 5
@@ -1080,6 +1090,112 @@ def solve_box_shared_host(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
     rc = _lib.qpb_solve_box_shared_host(ctypes.byref(d), p(H), p(f), p(lb), p(ub), p(x), p(lam), p(act), p(st), p(it))
     _check(rc, "qpb_solve_box_shared_host")
+    return Solution(x, lam, act, st, it)
+
+
+class BoxFactor(NamedTuple):
+    """One shared H of a batch of box QPs, factored once (qpb_factor_box): the input of ``solve_box_factored``."""
+    fac: object     # (factor_box_doubles(n),) float64: L, the rows of L^-T and their squared norms (layout internal)
+    n: int
+    status: object  # (1,) int32: OK or NOT_SPD
+
+
+def factor_box_doubles(n: int) -> int:
+    """Doubles a box factor buffer for n holds (qpb_factor_box_doubles; n <= 32)."""
+    k = int(_lib.qpb_factor_box_doubles(int(n)))
+    if k < 0:
+        _check(k, "qpb_factor_box_doubles")
+    return k
+
+
+def factor_box(H, *, stream=None) -> BoxFactor:
+    """Factor ONE H (n, n) for a whole batch of box QPs, once (qpb_factor_box): a
+    torch CUDA float64 tensor, one small launch, asynchronous on ``stream``.  The
+    result goes to ``solve_box_factored`` any number of times.  n <= 32."""
+    import torch
+    if not H.is_cuda:
+        raise ValueError("qpb.factor_box expects a CUDA (HIP) tensor; use factor_box_host for numpy")
+    if H.dtype != torch.float64 or not H.is_contiguous():
+        raise ValueError("inputs must be contiguous float64")
+    n = H.shape[-1]
+    if tuple(H.shape) != (n, n):
+        raise ValueError("shape mismatch: H must be (n, n)")
+    fac = torch.empty((factor_box_doubles(n),), dtype=torch.float64, device=H.device)
+    status = torch.empty((1,), dtype=torch.int32, device=H.device)
+    rc = _lib.qpb_factor_box(n, _ptr(H), _ptr(fac), _ptr(status), _stream_ptr(stream))
+    _check(rc, "qpb_factor_box")
+    return BoxFactor(fac, n, status)
+
+
+def solve_box_factored(F: BoxFactor, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0,
+                       out: Solution | None = None, stream=None) -> Solution:
+    """``solve_box_shared`` without the per-QP set-up (qpb_solve_box_factored):
+    ``F`` is ``factor_box(H)``, f (B, n) and lb / ub (B, n) or None are per QP.
+    The contract is ``solve_box_shared``'s except that x and lam may differ from
+    it by rounding and ``iters`` need not be the same."""
+    import torch
+    if not (f.is_cuda and F.fac.is_cuda):
+        raise ValueError("qpb.solve_box_factored expects CUDA (HIP) tensors; use solve_box_factored_host for numpy")
+    n = int(F.n)
+    for t in (f, lb, ub):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("inputs must be contiguous float64")
+        if t is not None and t.device != F.fac.device:
+            raise ValueError("the inputs must live on the factor's CUDA device")
+    if f.dim() != 2 or f.shape[1] != n or any(t is not None and t.shape != f.shape for t in (lb, ub)):
+        raise ValueError(f"shape mismatch: the factor is for n={n}")
+    if F.fac.dtype != torch.float64 or tuple(F.fac.shape) != (factor_box_doubles(n),) or not F.fac.is_contiguous():
+        raise ValueError(f"the factor buffer is not one for n={n}")
+    B, m = f.shape[0], 2 * n
+    if out is None:
+        out = _empty_solution(B, n, m, f.device)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    rc = _lib.qpb_solve_box_factored(ctypes.byref(d), _ptr(F.fac), _ptr(f), _ptr(lb), _ptr(ub), _ptr(out.x),
+                                     _ptr(out.lam), _ptr(out.active), _ptr(out.status), _ptr(out.iters),
+                                     _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_factored")
+    return out
+
+
+def factor_box_host(H) -> BoxFactor:
+    """numpy in / numpy out (qpb_factor_box_host): ``factor_box`` with a host array."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    n = H.shape[-1]
+    if H.shape != (n, n):
+        raise ValueError("shape mismatch: H must be (n, n)")
+    fac = np.zeros(factor_box_doubles(n))
+    st = np.zeros(1, dtype=np.int32)
+    rc = _lib.qpb_factor_box_host(n, H.ctypes.data_as(ctypes.c_void_p), fac.ctypes.data_as(ctypes.c_void_p),
+                                  st.ctypes.data_as(ctypes.c_void_p))
+    _check(rc, "qpb_factor_box_host")
+    return BoxFactor(fac, n, st)
+
+
+def solve_box_factored_host(F: BoxFactor, f, lb=None, ub=None, *, max_iter: int = 0,
+                            feas_tol: float = 0.0) -> Solution:
+    """numpy in / numpy out (qpb_solve_box_factored_host): ``solve_box_factored`` with host arrays."""
+    import numpy as np
+    n = int(F.n)
+    fac = np.ascontiguousarray(F.fac, dtype=np.float64)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    lb = None if lb is None else np.ascontiguousarray(lb, dtype=np.float64)
+    ub = None if ub is None else np.ascontiguousarray(ub, dtype=np.float64)
+    B = f.shape[0]
+    if f.shape != (B, n) or any(t is not None and t.shape != (B, n) for t in (lb, ub)) or \
+            fac.shape != (factor_box_doubles(n),):
+        raise ValueError(f"shape mismatch: the factor is for n={n}")
+    m = 2 * n
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, (m + 31) // 32), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, m, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_factored_host(ctypes.byref(d), p(fac), p(f), p(lb), p(ub), p(x), p(lam), p(act), p(st),
+                                          p(it))
+    _check(rc, "qpb_solve_box_factored_host")
     return Solution(x, lam, act, st, it)
 
 

@@ -24,7 +24,10 @@ per-QP set-up is gone from both passes.  The gradients are bit for bit those of
 and ub (``qpb.solve_box_backward``, n <= 32).  A 2-D ``H`` (n, n) is ONE matrix
 for the whole batch there as well: the solve is ``qpb.solve_box_shared``, the
 backward ``qpb.solve_box_shared_backward``, ``H.grad`` is (n, n) -- the sum over
-the batch -- and no (B, n, n) tensor is allocated in either pass.
+the batch -- and no (B, n, n) tensor is allocated in either pass.  With
+``prefactor=True`` (a 2-D H, n <= 32) the forward factors H once,
+``qpb.factor_box``, and solves with ``qpb.solve_box_factored``; the backward is
+``qpb.solve_box_shared_backward`` on the saved H, unchanged.
 
 ``solve_range(H, f, A, bl, bu, meq)`` is ``qpb.solve_range`` with gradients for
 H, f, A, bl and bu: the backward is ``qpb.solve_backward`` (or the shared one)
@@ -87,13 +90,17 @@ class BoxQPFunction(torch.autograd.Function):
     """x*(H, f, lb, ub) of min 1/2 x'Hx + f'x s.t. lb <= x <= ub."""
 
     @staticmethod
-    def forward(ctx, H, f, lb, ub, max_iter, feas_tol):
+    def forward(ctx, H, f, lb, ub, max_iter, feas_tol, prefactor=False):
         H, f = H.contiguous(), f.contiguous()
         lb = None if lb is None else lb.contiguous()
         ub = None if ub is None else ub.contiguous()
         ctx.shared = H.dim() == 2  # one H for the batch
-        forward = qpb.solve_box_shared if ctx.shared else qpb.solve_box
-        sol = forward(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        if prefactor:
+            # above n = 32 this raises QPBError(ERR_UNSUPPORTED)
+            sol = qpb.solve_box_factored(qpb.factor_box(H), f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        else:
+            forward = qpb.solve_box_shared if ctx.shared else qpb.solve_box
+            sol = forward(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
         ctx.has = (True, True, lb is not None, ub is not None)
         ctx.save_for_backward(H, sol.x, sol.active, sol.status)
         ctx.mark_non_differentiable(sol.status)
@@ -105,12 +112,12 @@ class BoxQPFunction(torch.autograd.Function):
         names = ("H", "f", "lb", "ub")
         wanted = [k for k, w, has in zip(names, ctx.needs_input_grad[:4], ctx.has) if w and has]
         if not wanted:
-            return (None,) * 6
+            return (None,) * 7
         sol = qpb.Solution(x, None, active, status, None)
         # on torch's current stream; above n = 32 this raises QPBError(ERR_UNSUPPORTED)
         backward = qpb.solve_box_shared_backward if ctx.shared else qpb.solve_box_backward
         gH, gf, glb, gub = backward(H, sol, gx.contiguous(), need=wanted)
-        return gH, gf, glb, gub, None, None
+        return gH, gf, glb, gub, None, None, None
 
 
 class RangeQPFunction(torch.autograd.Function):
@@ -181,7 +188,7 @@ def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: f
     return RangeQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol), bool(prefactor))
 
 
-def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0):
+def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):
     """Differentiable batched box solve (``qpb.solve_box`` with gradients):
     returns ``(x, status)``; ``x`` carries gradients to whichever of H, f, lb
     and ub require them, ``status`` (int32 per QP) is not differentiable.  A
@@ -193,8 +200,16 @@ def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.
     shared by the batch (``qpb.solve_box_shared``, with x bit for bit that of B
     copies), whose gradient (n, n) is the sum over the batch
     (``qpb.solve_box_shared_backward``), computed without a per-QP matrix; a
-    3-D H is the batched path unchanged."""
-    return BoxQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol))
+    3-D H is the batched path unchanged.  ``prefactor=True`` needs a 2-D H, else
+    ValueError, and n <= 32 (``QPBError(ERR_UNSUPPORTED)`` above): the forward
+    factors H once (``qpb.factor_box``) and solves with
+    ``qpb.solve_box_factored``, whose x may differ from the default's by
+    rounding; the backward is ``qpb.solve_box_shared_backward`` on the saved H,
+    unchanged.  The default is today's call, bit for bit."""
+    if prefactor:
+        if H.dim() != 2:
+            raise ValueError("prefactor=True needs a 2-D H (n, n): one matrix for the batch")
+    return BoxQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol), bool(prefactor))
 
 
 def solve(H, f, A=None, b=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):

@@ -16,6 +16,7 @@
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
  *   ... a box solve with ONE H for the whole batch         qpb_solve_box_shared, qpb_solve_box_shared_backward
+ *   ... a box solve with that H factored ONCE              qpb_factor_box, qpb_solve_box_factored
  *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
@@ -782,9 +783,10 @@ int qpb_solve_box_backward_host(const qpb_desc *desc, const double *H,
  * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
  * missing H, f, x, lam, active or status QPB_ERR_INVALID_ARG (lb, ub and iters
  * may be NULL); a missing device last.
- * Follow-ups: factoring the shared H ONCE for box solves, so that L and L^-T
- * are the same numbers for every QP (this call factors H per QP on purpose:
- * bit-for-bit equality with qpb_solve_box is its test); general rows beside a
+ * This call factors H per QP on purpose (bit-for-bit equality with
+ * qpb_solve_box is its test); with the shared H factored ONCE, so that L and
+ * L^-T are the same numbers for every QP: qpb_factor_box and
+ * qpb_solve_box_factored, below (n <= 32).  Follow-up: general rows beside a
  * box.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_box_shared(const qpb_desc *desc, const double *H, const double *f,
@@ -826,6 +828,8 @@ int qpb_solve_box_shared_host(const qpb_desc *desc, const double *H,
  * QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are looked at;
  * missing pointers QPB_ERR_INVALID_ARG (H, x, active and gx; at least one
  * output); a missing device last.
+ * The outputs of qpb_solve_box_factored, below, go to this call with the H the
+ * buffer was made from.
  * Follow-ups: the box backward above n = 32; a factored box backward.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_box_shared_backward(const qpb_desc *desc, const double *H,
@@ -840,6 +844,85 @@ int qpb_solve_box_shared_backward_host(const qpb_desc *desc, const double *H,
 				       const int32_t *status, const double *gx,
 				       double *gH, double *gf, double *glb,
 				       double *gub);
+
+/* ONE H for a batch of box QPs, factored ONCE.  With H shared, the set-up of
+ * every QP -- H = L L^T and the rows of L^-T, which are the rows of
+ * D = A L^-T for A = [I; -I] up to sign -- is the same numbers; qpb_factor_box
+ * computes them once into a box factor buffer, and qpb_solve_box_factored
+ * starts every QP from it: what is left per QP is y = L^-1 f, e = L^-T y and
+ * the slacks ub + e and -lb - e.
+ *
+ * The buffer `bxfac` holds a header ([0] 0 or QPB_NOT_SPD as a double, [1] n,
+ * [2] the padded n), L, the rows of L^-T and per row its squared norm, in the
+ * order the solve's lanes load them; it holds neither H nor A (the recovery
+ * x = -H^-1 (f + lam_u - lam_l) reads neither).  Its layout is internal
+ * (csrc/qpb_factor.h, bxfct) and belongs to one n: n <= 16 is
+ * qpb_gi_box.hip's, 16 < n <= 32 the BOX form of qpb_gi_wave.hip's.  It is NOT
+ * qpb_factor_shared's `fac`: a buffer of the other kind, or one made for
+ * another n, is the caller's error, like any wrongly sized array.  `bxfac` must
+ * be 16-byte aligned (hipMalloc's and torch's allocations are), else
+ * QPB_ERR_INVALID_ARG. */
+
+/* doubles a box factor buffer for n holds; < 0: a qpb_error (n < 1:
+ * QPB_ERR_INVALID_ARG; n > 32: QPB_ERR_UNSUPPORTED).  Pure host arithmetic. */
+int64_t qpb_factor_box_doubles(int32_t n);
+
+/* Factor ONE H (n x n) into `bxfac` (qpb_factor_box_doubles(n) doubles,
+ * device).  One small launch of one workgroup, asynchronous on `stream`: a
+ * solve queued behind it on the same stream needs no host synchronisation.
+ * Every element of the buffer is written, and nothing else.  fstatus (one
+ * int32, device, may be NULL): QPB_OK or QPB_NOT_SPD; a NaN in H gives
+ * QPB_NOT_SPD, as it does in the solve kernels.  L and L^-T are the values the
+ * unfactored kernels compute: each class's factor kernel runs that class's own
+ * load and sweep.  H is only read.
+ * Errors, in order: n < 1 QPB_ERR_INVALID_ARG; n > 32 QPB_ERR_UNSUPPORTED; H or
+ * bxfac missing QPB_ERR_INVALID_ARG; a misaligned bxfac QPB_ERR_INVALID_ARG; a
+ * missing device last. */
+int qpb_factor_box(int32_t n, const double *H, double *bxfac, int32_t *fstatus,
+		   void *stream);
+
+/* Same with host pointers; bxfac (host, any alignment) receives the buffer. */
+int qpb_factor_box_host(int32_t n, const double *H, double *bxfac,
+			int32_t *fstatus);
+
+/* qpb_solve_box_shared without the per-QP set-up, on a buffer of
+ * qpb_factor_box for desc->n.  The contract is that call's on the H the buffer
+ * was made from: the layouts with m = 2n (lam: upper bounds' multipliers
+ * first; active: ceil(2n/32) words per QP), what is written at every status,
+ * NaN and +-inf bounds or a NULL lb / ub as absent bounds, pinned variables and
+ * crossed bounds, lam >= 0 exactly, the default max_iter 4 (n + m) + 8,
+ * feas_tol per call.  A QP's outputs depend on its own f, lb and ub and on
+ * bxfac only: not on the batch size, on the QP's position, or on the other QPs
+ * of the launch, non-finite ones included.  Two things differ.  The outputs are
+ * not bit for bit qpb_solve_box_shared's: L and L^-T are the same numbers, but
+ * the slacks are formed from the stored rows and no longer inside the sweep, so
+ * x and lam differ by rounding; on a non-degenerate QP status and active are
+ * the same.  And iters may differ from the unfactored solve's.
+ * A buffer whose H was not SPD gives every QP QPB_NOT_SPD, with iters = 0,
+ * lam = 0 and active = 0.  The buffer is only read: any number of solves, on
+ * any streams, may use it at once.
+ * Errors, in order: the descriptor as qpb_solve_box (m != 2n
+ * QPB_ERR_INVALID_ARG); desc->flags != 0 QPB_ERR_INVALID_ARG; n > 32
+ * QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are looked at;
+ * missing pointers QPB_ERR_INVALID_ARG (bxfac, f, x, lam, active and status;
+ * lb, ub and iters may be NULL); a misaligned bxfac QPB_ERR_INVALID_ARG; a
+ * missing device last.
+ * The backward is qpb_solve_box_shared_backward on the H the buffer was made
+ * from, unchanged.  Limit: n <= 32.  Follow-up: the Gram class, 32 < n <= 128,
+ * whose set-up runs on the matrix cores and whose buffer would be a different
+ * object.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_box_factored(const qpb_desc *desc, const double *bxfac,
+			   const double *f, const double *lb, const double *ub,
+			   double *x, double *lam, uint32_t *active,
+			   int32_t *status, int32_t *iters, void *stream);
+
+/* Same with host pointers (bxfac included: the call uploads it). */
+int qpb_solve_box_factored_host(const qpb_desc *desc, const double *bxfac,
+				const double *f, const double *lb,
+				const double *ub, double *x, double *lam,
+				uint32_t *active, int32_t *status,
+				int32_t *iters);
 
 /* Reference-semantics solvers (qp_solvers.c replicas). */
 typedef enum qpb_ref_mode {
