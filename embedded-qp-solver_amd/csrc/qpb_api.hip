@@ -278,6 +278,14 @@ static int check_shared_bwd(const qpb_desc *d, int32_t shared) {
   return 0;
 }
 
+// The two passes of qpb_solve_shared_backward (glam == NULL: its launches and
+// nothing else) and of qpb_solve_backward_dual (glam given, m > 0, any `shared`,
+// 0 included: pass 1 is the DU forms), after the checks.  `what` names the call.
+static int shared_bwd_passes(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
+                             const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
+                             const double *glam, double *gH, double *gf, double *gA, double *gb, void *stream,
+                             const char *what);
+
 extern "C" int qpb_solve_shared_backward(const qpb_desc *d, int32_t shared, const double *H, const double *A,
                                          const double *x, const double *lam, const uint32_t *active,
                                          const int32_t *status, const double *gx, double *gH, double *gf, double *gA,
@@ -294,6 +302,48 @@ extern "C" int qpb_solve_shared_backward(const qpb_desc *d, int32_t shared, cons
   if (rc) return rc;
   rc = check_device();
   if (rc) return rc;
+  return shared_bwd_passes(d, shared, H, A, x, lam, active, status, gx, nullptr, gH, gf, gA, gb, stream,
+                           "qpb_solve_shared_backward");
+}
+
+// qpb_solve_backward_dual's argument rules after check_desc, up to the pointers
+static int check_bwd_dual(const qpb_desc *d, int32_t shared) {
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_backward_dual: flags must be 0 (got %d)", d->flags);
+  if (shared & ~(QPB_SHARED_H | QPB_SHARED_A))
+    return fail(QPB_ERR_INVALID_ARG,
+                "qpb_solve_backward_dual: shared must be a combination of QPB_SHARED_H and QPB_SHARED_A (got %d)",
+                shared);
+  if (qpb::route_bwd_dual(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "qpb_solve_backward_dual: n=%d m=%d outside the backward kernels (n<=%d, m<=%d)",
+                d->n, d->m, qpb::kBwdDualMaxN, qpb::kBwdDualMaxM);
+  return 0;
+}
+
+extern "C" int qpb_solve_backward_dual(const qpb_desc *d, int32_t shared, const double *H, const double *A,
+                                       const double *x, const double *lam, const uint32_t *active,
+                                       const int32_t *status, const double *gx, const double *glam, double *gH,
+                                       double *gf, double *gA, double *gb, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_dual(d, shared);
+  if (rc) return rc;
+  // no cotangent on lam: the call is qpb_solve_shared_backward, with its remaining rules
+  if (!glam || d->m == 0)
+    return qpb_solve_shared_backward(d, shared, H, A, x, lam, active, status, gx, gH, gf, gA, gb, stream);
+  if (d->batch == 0) return 0;
+  rc = check_bwd_arrays(d, H, A, x, lam, active, gx, gH, gf, gA, gb);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  return shared_bwd_passes(d, shared, H, A, x, lam, active, status, gx, glam, gH, gf, gA, gb, stream,
+                           "qpb_solve_backward_dual");
+}
+
+static int shared_bwd_passes(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
+                             const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
+                             const double *glam, double *gH, double *gf, double *gA, double *gb, void *stream,
+                             const char *what) {
+  int rc = 0;
   const qpb::Route r = qpb::route_shared_bwd(d->n, d->m);
   const long long n = d->n, m = d->m, B = d->batch;
   if (m == 0) gA = gb = nullptr;  // ignored
@@ -307,15 +357,17 @@ extern "C" int qpb_solve_shared_backward(const qpb_desc *d, int32_t shared, cons
     return qpb::for_each_chunk(
         B, r.step,
         [&](long long count, const double *Hc, const double *Ac, const double *xc, const double *lc,
-            const uint32_t *ac, const int32_t *sc, const double *gxc, double *gHc, double *gfc, double *gAc,
-            double *gbc) {
+            const uint32_t *ac, const int32_t *sc, const double *gxc, const double *glc, double *gHc, double *gfc,
+            double *gAc, double *gbc) {
           qpb_desc c = *d;
           c.batch = count;
-          const hipError_t e = qpb_launch_kkt_bwd_shared(&c, sH, sA, Hc, Ac, xc, lc, ac, sc, gxc, gHc, gfc, gAc, gbc, st);
-          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_shared_backward launch");
+          const hipError_t e =
+              glam ? qpb_launch_kkt_bwd_dual(&c, sH, sA, Hc, Ac, xc, lc, ac, sc, gxc, glc, gHc, gfc, gAc, gbc, st)
+                   : qpb_launch_kkt_bwd_shared(&c, sH, sA, Hc, Ac, xc, lc, ac, sc, gxc, gHc, gfc, gAc, gbc, st);
+          return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
         },
         qpb::required(H, sH), qpb::optional(A, sA), qpb::required(x, n), qpb::optional(lam, m),
-        qpb::optional(active, (m + 31) / 32), qpb::optional(status, 1), qpb::required(gx, n),
+        qpb::optional(active, (m + 31) / 32), qpb::optional(status, 1), qpb::required(gx, n), qpb::optional(glam, m),
         qpb::optional(gH1, n * n), qpb::optional(gf1, n), qpb::optional(gA1, m * n), qpb::optional(gb1, m));
   };
   if (!sumH && !sumA) return pass1(gf, gb);  // the summed gradients are not wanted: pass 1 alone
@@ -332,7 +384,7 @@ extern "C" int qpb_solve_shared_backward(const qpb_desc *d, int32_t shared, cons
     return qpb_launch_kkt_bwd_sum(d, x, dx, gbs, lam, active, status, slots, sumH, sumA, st);
   });
   if (rc) return rc;
-  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_shared_backward sum launch");
+  return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s sum launch: %s", what, hipGetErrorString(e));
 }
 
 extern "C" int qpb_solve_box(const qpb_desc *d, const double *H, const double *f, const double *lb,
@@ -1195,11 +1247,12 @@ extern "C" int qpb_solve_range_factored_host(const qpb_desc *d, int32_t meq, con
   return 0;
 }
 
-// qpb_solve_backward_host and qpb_solve_shared_backward_host (shared > 0: a
-// shared operand and its gradient are one matrix): copy in, run, copy out
+// qpb_solve_backward_host, qpb_solve_shared_backward_host (shared > 0: a
+// shared operand and its gradient are one matrix) and qpb_solve_backward_dual_host
+// (glam, may be NULL): copy in, run, copy out
 static int backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
                          const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
-                         double *gH, double *gf, double *gA, double *gb);
+                         const double *glam, double *gH, double *gf, double *gA, double *gb);
 
 extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const double *A, const double *x,
                                        const double *lam, const uint32_t *active, const int32_t *status,
@@ -1208,7 +1261,7 @@ extern "C" int qpb_solve_backward_host(const qpb_desc *d, const double *H, const
   if (rc) return rc;
   rc = check_bwd(d);
   if (rc) return rc;
-  return backward_host(d, 0, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+  return backward_host(d, 0, H, A, x, lam, active, status, gx, nullptr, gH, gf, gA, gb);
 }
 
 extern "C" int qpb_solve_shared_backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A,
@@ -1221,12 +1274,24 @@ extern "C" int qpb_solve_shared_backward_host(const qpb_desc *d, int32_t shared,
   if (rc) return rc;
   shared = shared_of(d, shared);
   if (shared == 0) return qpb_solve_backward_host(d, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
-  return backward_host(d, shared, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+  return backward_host(d, shared, H, A, x, lam, active, status, gx, nullptr, gH, gf, gA, gb);
+}
+
+extern "C" int qpb_solve_backward_dual_host(const qpb_desc *d, int32_t shared, const double *H, const double *A,
+                                            const double *x, const double *lam, const uint32_t *active,
+                                            const int32_t *status, const double *gx, const double *glam, double *gH,
+                                            double *gf, double *gA, double *gb) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_dual(d, shared);
+  if (rc) return rc;
+  if (!glam || d->m == 0) return qpb_solve_shared_backward_host(d, shared, H, A, x, lam, active, status, gx, gH, gf, gA, gb);
+  return backward_host(d, shared, H, A, x, lam, active, status, gx, glam, gH, gf, gA, gb);
 }
 
 static int backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *A, const double *x,
                          const double *lam, const uint32_t *active, const int32_t *status, const double *gx,
-                         double *gH, double *gf, double *gA, double *gb) {
+                         const double *glam, double *gH, double *gf, double *gA, double *gb) {
   int rc;
   if (d->batch == 0) return 0;
   rc = check_bwd_arrays(d, H, A, x, lam, active, gx, gH, gf, gA, gb);  // host pointers: the same rules
@@ -1234,7 +1299,7 @@ static int backward_host(const qpb_desc *d, int32_t shared, const double *H, con
   rc = check_device();
   if (rc) return rc;
   const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
-  DevBuf dH, dA, dx, dl, da, ds, dg, oH, of, oA, ob;
+  DevBuf dH, dA, dx, dl, da, ds, dg, dgl, oH, of, oA, ob;
   const size_t BH = (shared & QPB_SHARED_H) ? 1 : B, BA = (shared & QPB_SHARED_A) ? 1 : B;
   HIPCHK(up(dH, H, BH * n * n * 8), "H");
   HIPCHK(up(dA, m ? A : nullptr, BA * m * n * 8), "A");
@@ -1243,13 +1308,14 @@ static int backward_host(const qpb_desc *d, int32_t shared, const double *H, con
   HIPCHK(up(da, m ? active : nullptr, B * w * 4), "active");
   HIPCHK(up(ds, status, B * 4), "status");
   HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(up(dgl, m ? glam : nullptr, B * m * 8), "glam");
   HIPCHK(alloc(oH, gH, BH * n * n * 8), "gH");
   HIPCHK(alloc(of, gf, B * n * 8), "gf");
   HIPCHK(alloc(oA, m ? gA : nullptr, BA * m * n * 8), "gA");
   HIPCHK(alloc(ob, m ? gb : nullptr, B * m * 8), "gb");
-  rc = qpb_solve_shared_backward(d, shared, (double *)dH.p, (double *)dA.p, (double *)dx.p, (double *)dl.p,
-                                 (uint32_t *)da.p, (int32_t *)ds.p, (double *)dg.p, (double *)oH.p, (double *)of.p,
-                                 (double *)oA.p, (double *)ob.p, nullptr);
+  rc = qpb_solve_backward_dual(d, shared, (double *)dH.p, (double *)dA.p, (double *)dx.p, (double *)dl.p,
+                               (uint32_t *)da.p, (int32_t *)ds.p, (double *)dg.p, (double *)dgl.p, (double *)oH.p,
+                               (double *)of.p, (double *)oA.p, (double *)ob.p, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "qpb_solve_backward_host kernel");
   HIPCHK(down(gH, oH, BH * n * n * 8), "gH D2H");

@@ -98,14 +98,24 @@ static_assert(QPB_MAX_M < (1 << kShShift) && (3 << kShShift) > 0);
 // loaded and no sweep runs.  From the orthogonalisation on the code is one.
 template <int FM>
 using Form = std::integral_constant<int, FM>;
-template <int MR, bool N16, bool SH = false, class... FMP>
+// GL (empty, or one const double *: the DU form, qpb_solve_backward_dual): the
+// cotangent glam on the multipliers, B x m in lam's layout, as the lower
+// right-hand side of the KKT system.  Its entries on the rows of W are
+// scattered to the rows' positions (g), R^T w = g is solved on R's columns,
+// Q w leaves z after the two projection passes and w joins the right-hand side
+// of the R solve.  Deduced from the launch's trailing argument; the other
+// forms have no such argument and none of this code.
+template <int MR, bool N16, bool SH = false, class... FMP, class... GL>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
     const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
-    double *__restrict__ gbg, int n, int m, long long batch) {
+    double *__restrict__ gbg, int n, int m, long long batch, GL... glamg) {
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
+  constexpr bool DU = sizeof...(GL) == 1;
+  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM != 0),
+                "glam is one array, beside H and A");
   __shared__ double lds[QPB * SLOT];
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -134,6 +144,16 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   uint32_t W = (m > 0 && ok) ? form_mask<FM>(actg, g) : 0u;
   if (m < 32) W &= (1u << m) - 1u;
   const double gv = form_gx<FM>(gxg, g * n + lc);
+  [[maybe_unused]] double gl[MR];  // DU: glam of the lane's rows, 0 outside W (whatever it holds there)
+  if constexpr (DU) {
+    const double *__restrict__ glq = (glamg, ...) + g * (long long)m;  // (the form has m > 0)
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+      const int row = l + NL * r;
+      const double v = glq[row < m ? row : 0];
+      gl[r] = ((W >> row) & 1u) ? v : 0.0;
+    }
+  }
   double Lr[NL];     // row l of H, becomes row l of L
   double E[MR][NL];  // rows l, l + 16 of A, become rows of D = A L^{-T}
   double ya, ul, invLd;
@@ -386,6 +406,51 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   project(z, cu, qmax);
   project(z, cu, qmax);
   z = -z;
+  if constexpr (DU) {
+    // ---- g: glam of the kept rows at their positions, through the exchange
+    // row (0 past cnt; a skipped row has no position and its glam goes nowhere)
+    wave_lds_sync();
+    xch[l] = 0.0;
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < MR; ++r)
+      if (pos[r] >= 0) xch[pos[r]] = gl[r];
+    wave_lds_sync();
+    double w = xch[l];
+    // ---- R^T w = g, column-oriented: lane t holds column t of R above the
+    // diagonal (the slot's layout), step s takes the finished w_s from lane s
+    // and the lanes behind it subtract R[s][t] w_s.  1 / R_tt is 0 past cnt.
+    double Rc[NL];
+    lds_row16(&R[l * NL], Rc);
+    wave_lds_sync();
+    // The product is read from lane s by the FMA itself, as in
+    // back_subst_step: it was written just before, so fmac_bc_nop issues the
+    // DPP read hazard's wait states.
+    {
+      const double ninv = -invRd;
+      unroll<NL - 1>([&](auto S) {
+        constexpr int s = S;
+        if (s + 1 < qmax) fmac_bc_nop<s>(w, w * ninv, l > s ? Rc[s] : 0.0);
+      });
+    }
+    w *= invRd;
+    // ---- z -= Q w, in-lane on the lane's components of the q_s (w_s from lane
+    // s, fused); cu -= w makes the right-hand side of the R solve below
+    // -Q^T u + w
+    {
+      // (pinned: left as -w, the compiler reassembles the pair from w's low
+      // word and the flipped high word in front of every other FMA, inside
+      // the hazard's window)
+      double nw = -w;
+      pin(nw);
+      dpp_ready(nw);
+      unroll<NL>([&](auto S) {
+        constexpr int s = S;
+        if (s < qmax) fmac_bc<s>(z, nw, Qt[s]);
+      });
+    }
+    cu -= w;
+  }
   double y;  // dlam of position l
   {
     const double ninv = -invRd;
@@ -533,14 +598,20 @@ __device__ __forceinline__ double wave_sum(double t) {
 // gbg); FM == 2 (Hg is the buffer) copies L's image into LDS, takes u from the
 // stored L and 1 / L_kk by the operations of the factorisation loop, and an
 // active row's v is one load.
-template <bool SH = false, class... FMP>
+// GL: the dense kernel's DU form.  Lane r < m holds glam of row r; g goes to
+// the rows' positions through vb, R^T w = g runs on R above L's diagonal as the
+// R solve does, and Q w leaves z through cb, by the loop of a projection pass.
+template <bool SH = false, class... FMP, class... GL>
 __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
     const double *__restrict__ gxg, double *__restrict__ gHg, double *__restrict__ gfg, double *__restrict__ gAg,
-    double *__restrict__ gbg, int n, int m, long long batch) {
+    double *__restrict__ gbg, int n, int m, long long batch, GL... glamg) {
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
+  constexpr bool DU = sizeof...(GL) == 1;
+  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM != 0),
+                "glam is one array, beside H and A");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -569,6 +640,11 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   }
   W = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(W >> 32)) << 32) |
       (unsigned)__builtin_amdgcn_readfirstlane((int)W);
+  [[maybe_unused]] double glv = 0.0;  // DU: glam of row `lane`, 0 outside W (whatever it holds there)
+  if constexpr (DU) {
+    const double v = (glamg, ...)[g * m + (lane < m ? lane : 0)];  // (the form has m > 0)
+    glv = ((W >> lane) & 1ull) ? v : 0.0;
+  }
   [[maybe_unused]] const bfct::Layout fy = bfct::layout(FM != 0 ? n : 17, m);  // the wave class's offsets
   if constexpr (FM == 2) {
     // L's image as the factor kernel left it, Q zero
@@ -731,7 +807,36 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   project(z, cu);
   project(z, cu);
   z = -z;
+  [[maybe_unused]] double wv = 0.0;  // DU: w of position `lane` (0 past cnt)
+  if constexpr (DU) {
+    // g: glam of the kept rows at their positions (a skipped row has none)
+    wave_lds_sync();
+    if (low) vb[lane] = 0.0;
+    wave_lds_sync();
+    const int p = (int)posb[lane];
+    if (p >= 0) vb[p] = glv;
+    wave_lds_sync();
+    wv = lane < cnt ? vb[lane] : 0.0;
+    // R^T w = g: step t finishes w_t and the positions behind it subtract R[t][lane] w_t
+    const double iw = lane < cnt ? ir[lane] : 0.0;
+    for (int t = 0; t < cnt; ++t) {
+      const double wt = readlane_d(wv * iw, t);
+      if (lane == t) wv = wt;
+      else if (lane > t && lane < cnt) wv = __builtin_fma(-Lm[t * WS + lane], wt, wv);
+    }
+    // z -= Q w, the last loop of a projection pass on w (the q_s past cnt are zero)
+    wave_lds_sync();
+    if (low) cb[lane] = wv;
+    wave_lds_sync();
+    if (low) {
+      for (int s0 = 0; s0 < cnt; s0 += 4) {
+#pragma unroll
+        for (int s = s0; s < s0 + 4; ++s) z = __builtin_fma(-cb[s], Qm[s * WS + lane], z);
+      }
+    }
+  }
   double y = -cu;  // the right-hand side, then dlam of position `lane`
+  if constexpr (DU) y += wv;
   const double invRd = lane < cnt ? ir[lane] : 0.0;
   for (int t = cnt - 1; t >= 0; --t) {
     const double yt = readlane_d(y * invRd, t);
@@ -822,6 +927,38 @@ extern "C" hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long str
     hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), true>), dim3((unsigned)blocks), dim3(64), 0,
                        stream, H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch);
   });
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_backward_dual (m > 0 and glam given): the DU forms, plain
+// where both strides are the batched ones and SH otherwise
+extern "C" hipError_t qpb_launch_kkt_bwd_dual(const qpb_desc *d, long long strideH, long long strideA,
+                                              const double *H, const double *A, const double *x, const double *lam,
+                                              const uint32_t *active, const int32_t *status, const double *gx,
+                                              const double *glam, double *gH, double *gf, double *gA, double *gb,
+                                              hipStream_t stream) {
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | (strideA == 0 ? QPB_SHARED_A : 0);
+  const int mm = d->m | (shared << qpb::bwd::kShShift);
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  const bool wave = d->n > 16 || d->m > 32;
+  if (wave && shared) {
+    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<true>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x,
+                       lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch, glam);
+  } else if (wave) {
+    hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, A, x, lam,
+                       active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch, glam);
+  } else if (shared) {
+    qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+      hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), true>), dim3((unsigned)blocks), dim3(64), 0,
+                         stream, H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, mm, (long long)d->batch,
+                         glam);
+    });
+  } else {
+    qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+      hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16()>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                         H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch, glam);
+    });
+  }
   return hipGetLastError();
 }
 

@@ -114,6 +114,13 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_shared(const qpb_desc *d, long long s
                                                   const double *lam, const uint32_t *active, const int32_t *status,
                                                   const double *gx, double *gH, double *gf, double *gA, double *gb,
                                                   hipStream_t stream);
+// qpb_solve_backward_dual, pass 1 (d->m > 0, glam not NULL): the DU forms of the
+// same kernels on the same strides, with glam (B x m) as the lower right-hand side
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_dual(const qpb_desc *d, long long strideH, long long strideA,
+                                                const double *H, const double *A, const double *x, const double *lam,
+                                                const uint32_t *active, const int32_t *status, const double *gx,
+                                                const double *glam, double *gH, double *gf, double *gA, double *gb,
+                                                hipStream_t stream);
 // ... pass 2 (qpb_kkt_bwd_sum.hip): the n x n and / or m x n sums over the whole
 // batch from pass 1's gf (dx) and gb; slots: qpb::sum_plan(batch).slots times
 // qpb::sum_slot_doubles(n, m) doubles of scratch

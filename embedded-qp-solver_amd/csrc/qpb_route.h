@@ -212,6 +212,25 @@ static_assert(route_shared(kSharedMaxN, kSharedMaxM).step > 0 && route_shared(kS
 static_assert(route_shared_bwd(kSharedMaxN, kSharedMaxM).step > 0 && route_shared_bwd(kSharedMaxN + 1, 1).step == 0 &&
               route_shared_bwd(1, kSharedMaxM + 1).step == 0);
 
+// qpb_solve_backward_dual: route_shared_bwd's classes, whose DU forms (plain and
+// SH) take glam; above them there is none: step 0, and the call is unsupported.
+constexpr Route route_bwd_dual(int n, int m) {
+  const Route r = route_shared_bwd(n, m);
+  return {r.kernel, r.step};
+}
+constexpr int kBwdDualMaxN = kSharedMaxN, kBwdDualMaxM = kSharedMaxM;
+
+static_assert(route_bwd_dual(1, 0).kernel == Kernel::gi_dense && route_bwd_dual(16, 32).kernel == Kernel::gi_dense);
+static_assert(route_bwd_dual(16, 33).kernel == Kernel::gi_wave && route_bwd_dual(17, 0).kernel == Kernel::gi_wave &&
+              route_bwd_dual(32, 64).kernel == Kernel::gi_wave);
+static_assert(route_bwd_dual(16, 32).kernel == route_shared_bwd(16, 32).kernel &&
+              route_bwd_dual(16, 32).step == route_shared_bwd(16, 32).step &&
+              route_bwd_dual(32, 64).kernel == route_shared_bwd(32, 64).kernel &&
+              route_bwd_dual(32, 64).step == route_shared_bwd(32, 64).step);
+static_assert(route_bwd_dual(33, 0).step == 0 && route_bwd_dual(16, 65).step == 0 && route_bwd_dual(129, 32).step == 0);
+static_assert(route_bwd_dual(kBwdDualMaxN, kBwdDualMaxM).step > 0 && route_bwd_dual(kBwdDualMaxN + 1, 1).step == 0 &&
+              route_bwd_dual(1, kBwdDualMaxM + 1).step == 0);
+
 // qpb_factor_shared and qpb_solve_factored: route_shared's classes, whose
 // factor kernel writes and whose factored form reads the class's own layout of
 // the buffer (qpb_factor.h decides the class by the same two limits); above

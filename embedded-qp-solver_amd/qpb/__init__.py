@@ -15,6 +15,8 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve_backward(H, A, sol, gx) -> qpb_solve_backward (gradients of a solve; autograd: qpb.diff)
     solve_shared(H, f, A, b, meq) -> qpb_solve_shared (a 2-D H and / or A: one matrix for the whole batch)
     solve_shared_backward(H, A, sol, gx) -> qpb_solve_shared_backward (a shared operand's gradient summed over the batch)
+    solve_backward_dual(H, A, sol, gx, glam) -> qpb_solve_backward_dual (a cotangent on lam as well; autograd: qpb.diff.solve_dual)
+    solve_tangent(H, A, sol, df, db) -> qpb_solve_backward_dual (the tangent of (x*, lam*) along (df, db))
     solve_box_backward(H, sol, gx) -> qpb_solve_box_backward (gradients of a box solve, n <= 32)
     solve_box_shared(H, f, lb, ub) -> qpb_solve_box_shared (a box solve with ONE H (n, n) for the whole batch, n <= 128)
     solve_box_shared_backward(H, sol, gx) -> qpb_solve_box_shared_backward (its gradients, gH (n, n) summed over the batch, n <= 32)
@@ -100,6 +102,10 @@ _lib.qpb_solve_shared_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32]
 _lib.qpb_solve_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_shared_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_backward_dual.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 13
+_lib.qpb_solve_backward_dual.restype = ctypes.c_int
+_lib.qpb_solve_backward_dual_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 12
+_lib.qpb_solve_backward_dual_host.restype = ctypes.c_int
 _lib.qpb_factor_backward_doubles.argtypes = [ctypes.c_int32, ctypes.c_int32]
 _lib.qpb_factor_backward_doubles.restype = ctypes.c_int64
 _lib.qpb_factor_shared_backward.argtypes = [ctypes.c_int32, ctypes.c_int32] + [_vp] * 5
@@ -808,6 +814,104 @@ def solve_shared_backward_host(H, A, sol: Solution, gx, *, need=NEED_ALL):
                                              p(gH), p(gf), p(gA), p(gb))
     _check(rc, "qpb_solve_shared_backward_host")
     return gH, gf, gA, gb
+
+
+def solve_backward_dual(H, A, sol: Solution, gx, glam, *, need=NEED_ALL, stream=None):
+    """``solve_shared_backward`` for a loss that also reads the multipliers
+    (qpb_solve_backward_dual): ``glam = dl/dlam`` (B, m), in ``sol.lam``'s layout
+    and sign convention, is the lower right-hand side of the same KKT system,
+    and (gH, gf, gA, gb) are ``solve_backward``'s formulas on its solution.
+    A 2-D ``H`` or ``A`` is shared and its gradient is ONE matrix, the sum over
+    the batch, as in ``solve_shared_backward``.  ``glam`` outside the active set
+    and of QPs whose status is not OK is ignored, whatever it holds.
+    ``glam=None`` (or m = 0) is ``solve_shared_backward(H, A, sol, gx)``, bit for
+    bit.  n <= 32 and m <= 64."""
+    import torch
+    B, n, m, shared = _shared_shape("qpb.solve_backward_dual", H, gx, A, None if A is None else sol.lam)
+    need = _need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if m and (not sol.active.is_contiguous() or sol.active.shape != (B, (m + 31) // 32)
+              or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(m/32)) tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    if glam is not None and (not glam.is_cuda or glam.dtype != torch.float64 or not glam.is_contiguous()
+                             or glam.device != gx.device or tuple(glam.shape) != (B, m)):
+        raise ValueError("glam must be a contiguous float64 CUDA tensor of shape (B, m) on gx's device, or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(*H.shape) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    gA = new(*A.shape) if m and "A" in need else None
+    gb = new(B, m) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None  # m == 0 and only A / b wanted
+    d = Desc(n, m, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_backward_dual(ctypes.byref(d), shared, _ptr(H), _ptr(A) if m else None, _ptr(sol.x),
+                                      _ptr(sol.lam) if m else None, _ptr(sol.active) if m else None,
+                                      _ptr(sol.status), _ptr(gx), _ptr(glam) if m else None, _ptr(gH), _ptr(gf),
+                                      _ptr(gA), _ptr(gb), _stream_ptr(stream))
+    _check(rc, "qpb_solve_backward_dual")
+    return gH, gf, gA, gb
+
+
+def solve_backward_dual_host(H, A, sol: Solution, gx, glam, *, need=NEED_ALL):
+    """numpy in / numpy out (qpb_solve_backward_dual_host): ``solve_backward_dual`` with host arrays."""
+    import numpy as np
+    need = _need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    m = 0 if A is None else A.shape[-2]
+    lam = act = None
+    if m:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        lam = np.ascontiguousarray(sol.lam, dtype=np.float64)
+        act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    glam = None if glam is None or not m else np.ascontiguousarray(glam, dtype=np.float64)
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if m and A.ndim == 2 else 0)
+    if H.shape not in ((n, n), (B, n, n)) or x.shape != (B, n) or (m and A.shape not in ((m, n), (B, m, n))) or (
+            glam is not None and glam.shape != (B, m)):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros(H.shape) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    gA = np.zeros(A.shape) if m and "A" in need else None
+    gb = np.zeros((B, m)) if m and "b" in need else None
+    if gH is None and gf is None and gA is None and gb is None:
+        return None, None, None, None
+    d = Desc(n, m, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_backward_dual_host(ctypes.byref(d), shared, p(H), p(A), p(x), p(lam), p(act), p(st), p(gx),
+                                           p(glam), p(gH), p(gf), p(gA), p(gb))
+    _check(rc, "qpb_solve_backward_dual_host")
+    return gH, gf, gA, gb
+
+
+def solve_tangent(H, A, sol: Solution, df, db=None, *, stream=None):
+    """The forward sensitivity of a solve: the tangent ``(dx, dlam)`` of
+    (x*, lam*) along a change ``df`` (B, n) of f and ``db`` (B, m) of b, at fixed
+    active set.  Differentiating H x + f + A_W^T lam = 0, A_W x = b_W gives
+    K [dx; dlam_W] = -[df; -db_W] with the KKT matrix K of ``solve_backward``,
+    which is symmetric: the tangent is ONE call of ``solve_backward_dual`` with
+    ``gx = df``, ``glam = -db`` and ``need = ("f", "b")``, and
+    ``(dx, dlam) = (gf, -gb)``.  ``dlam`` is 0 outside the active set, and both
+    are 0 for a QP whose status is not OK.  ``db=None`` is db = 0 and runs
+    ``solve_backward``'s kernels.  With A None (m = 0) ``dlam`` is None.  For an
+    MPC law u*(x0), with f and b affine in the state x0, this is the local
+    affine law u* + K (x0 - x0*) one column at a time."""
+    import contextlib
+
+    import torch
+    m = 0 if A is None else A.shape[-2]
+    # (the two negations run on the call's stream as well)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        glam = None if db is None or not m else -db
+        _, dx, _, gb = solve_backward_dual(H, A, sol, df, glam, need=("f", "b"), stream=stream)
+        return dx, (None if gb is None else -gb)
 
 
 class BackwardFactor(NamedTuple):

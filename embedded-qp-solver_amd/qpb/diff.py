@@ -35,6 +35,12 @@ on the range solve's outputs, its ``gb`` routed to ``bl`` or ``bu`` by the
 ``lower`` bits.  ``prefactor=True`` (a 2-D H and a 2-D A) factors once per
 forward and solves with ``qpb.solve_range_factored``; the backward is the
 factored one in the same way.
+
+``solve_dual(H, f, A, b, meq)`` and ``solve_range_dual(H, f, A, bl, bu, meq)``
+return ``(x, lam, status)`` with x AND lam differentiable: the backward is
+``qpb.solve_backward_dual`` (qpb_solve_backward_dual, the same KKT system with
+the cotangent on lam as its lower right-hand side).  A loss that does not read
+lam takes the backward of ``solve`` / ``solve_range``, bit for bit.
 """
 from __future__ import annotations
 
@@ -164,6 +170,112 @@ class RangeQPFunction(torch.autograd.Function):
             if want[4]:
                 gbu = torch.where(low, zero, gb)
         return gH, gf, gA, gbl, gbu, None, None, None, None
+
+
+def _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted):
+    """The backward call of the forms that return lam: an unused lam arrives as
+    None and takes ``solve_backward``'s kernels, an unused x is a zero cotangent."""
+    sol = qpb.Solution(x, lam, active, status, None)
+    gx = torch.zeros_like(x) if gx is None else gx.contiguous()
+    if glam is None:
+        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
+        return backward(H, A, sol, gx, need=wanted)
+    # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
+    return qpb.solve_backward_dual(H, A, sol, gx, glam.contiguous(), need=wanted)
+
+
+class DualQPFunction(torch.autograd.Function):
+    """(x*, lam*)(H, f, A, b) of min 1/2 x'Hx + f'x s.t. A[:meq] x = b[:meq], A[meq:] x <= b[meq:]."""
+
+    @staticmethod
+    def forward(ctx, H, f, A, b, meq, max_iter, feas_tol):
+        H, f, A, b = H.contiguous(), f.contiguous(), A.contiguous(), b.contiguous()
+        ctx.shared = H.dim() == 2 or A.dim() == 2
+        if ctx.shared:
+            sol = qpb.solve_shared(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
+        else:
+            sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.lam, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, glam, _gstatus):
+        H, A, x, lam, active, status = ctx.saved_tensors
+        wanted = [k for k, w in zip("HfAb", ctx.needs_input_grad[:4]) if w]
+        if not wanted or (gx is None and glam is None):
+            return (None,) * 7
+        gH, gf, gA, gb = _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted)
+        return gH, gf, gA, gb, None, None, None
+
+
+class RangeDualQPFunction(torch.autograd.Function):
+    """(x*, lam*)(H, f, A, bl, bu) of ``RangeQPFunction``'s problem, lam signed."""
+
+    @staticmethod
+    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol):
+        H, f, A = H.contiguous(), f.contiguous(), A.contiguous()
+        bl = None if bl is None else bl.contiguous()
+        bu = None if bu is None else bu.contiguous()
+        # above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
+        sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.shared = H.dim() == 2 or A.dim() == 2
+        ctx.has = (True, True, True, bl is not None, bu is not None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.lower, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.lam, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, glam, _gstatus):
+        H, A, x, lam, active, lower, status = ctx.saved_tensors
+        want = [w and has for w, has in zip(ctx.needs_input_grad[:5], ctx.has)]
+        wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if want[3] or want[4] else [])
+        if not wanted or (gx is None and glam is None):
+            return (None,) * 8
+        gH, gf, gA, gb = _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted)
+        gbl = gbu = None
+        if gb is not None:
+            # as in RangeQPFunction: bl where the `lower` bit is set, bu everywhere else
+            m = gb.shape[1]
+            rows = torch.arange(m, device=gb.device)
+            low = ((lower[:, rows // 32] >> (rows % 32)) & 1).bool()
+            zero = torch.zeros_like(gb)
+            if want[3]:
+                gbl = torch.where(low, gb, zero)
+            if want[4]:
+                gbu = torch.where(low, zero, gb)
+        return gH, gf, gA, gbl, gbu, None, None, None
+
+
+def solve_dual(H, f, A, b, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+    """``solve`` that also returns the multipliers, differentiably: returns
+    ``(x, lam, status)``; ``x`` and ``lam`` (B, m, H x + f + A' lam = 0) both carry
+    gradients to whichever of H, f, A and b require them -- shadow prices,
+    constraint-tightness penalties and dual objectives can enter the loss.  The
+    backward is ``qpb.solve_backward_dual`` on the two cotangents at fixed active
+    set; a loss that does not read ``lam`` runs ``solve``'s backward, bit for
+    bit, and one that does not read ``x`` has gx = 0.  A 2-D H (n, n) and / or A
+    (m, n) is shared by the batch, its gradient the sum over the batch.  QPs whose
+    status is not OK contribute zero gradients.  n <= 32 and m <= 64 in the
+    backward (``QPBError(ERR_UNSUPPORTED)`` above).  A is required (without rows
+    there is no lam: use ``solve``); no ``prefactor`` yet."""
+    if A is None or b is None:
+        raise ValueError("qpb.diff.solve_dual needs A and b: without rows there are no multipliers (use solve)")
+    return DualQPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol))
+
+
+def solve_range_dual(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+    """``solve_range`` that also returns the signed multipliers, differentiably:
+    returns ``(x, lam, status)`` with ``lam`` in ``qpb.solve_range``'s convention
+    (H x + f + A' lam = 0: >= 0 on a row active at bu, <= 0 at bl).  The backward
+    is ``qpb.solve_backward_dual`` on the two cotangents; its ``gb`` goes to
+    ``bl`` where the ``lower`` bit is set and to ``bu`` everywhere else, exactly
+    as in ``solve_range``.  A bound passed as None gets no gradient.  A loss that
+    does not read ``lam`` gets ``solve_range``'s gradients bit for bit.  n <= 32
+    and m <= 64; no ``prefactor`` yet."""
+    return RangeDualQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol))
 
 
 def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,

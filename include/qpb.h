@@ -13,6 +13,7 @@
  *   north_star active-set over (H, f, A, b)              qpb_solve(m > 0)
  *   ... with equality rows, solve_qp(P, q, G, h, A, b)    qpb_solve_eq
  *   ... differentiated (dl/dH, dl/df, dl/dA, dl/db)        qpb_solve_backward
+ *   ... for a loss that reads lam too; the f / b tangent    qpb_solve_backward_dual
  *   ... the box solve (dl/dH, dl/df, dl/dlb, dl/dub)       qpb_solve_box_backward
  *   ... with ONE H and / or A for the whole batch          qpb_solve_shared, qpb_solve_shared_backward
  *   ... a box solve with ONE H for the whole batch         qpb_solve_box_shared, qpb_solve_box_shared_backward
@@ -465,6 +466,70 @@ int qpb_solve_shared_backward_host(const qpb_desc *desc, int32_t shared,
 				   const int32_t *status, const double *gx,
 				   double *gH, double *gf, double *gA,
 				   double *gb);
+
+/* qpb_solve_shared_backward for a loss l(x, lam) that also reads the
+ * multipliers: the same KKT system at FIXED active set with a full right-hand
+ * side,
+ *
+ *     [ H    A_W^T ] [ dx   ]     [ gx     ]
+ *     [ A_W   0    ] [ dlam ] = - [ glam_W ]
+ *
+ * and qpb_solve_backward's output formulas on its solution, unchanged:
+ * gf = dx, gH = 1/2 (dx x^T + x dx^T), gb_i = -dlam_i,
+ * gA_i = dlam_i x^T + lam_i dx^T (i in W, else 0).  K is symmetric, so the same
+ * call is the forward sensitivity (the tangent) of (x*, lam*) along a change
+ * (df, db) of f and b: with gx = df and glam = -db, gf is dx* and -gb is dlam*.
+ *   glam            B x m, in lam's layout and lam's sign convention
+ *                   (H x + f + A^T lam = 0 with the caller's A): the signed lam
+ *                   of qpb_solve_range needs nothing special.
+ *   glam == NULL,   the call is qpb_solve_shared_backward: the same kernels,
+ *   or m == 0       the same outputs bit for bit (shared == 0:
+ *                   qpb_solve_backward).
+ *   glam outside W  ignored, whatever it holds, NaN included.  So is the glam
+ *                   of a row the orthogonalisation skips (a dependent row, a
+ *                   row met after n independent ones): dlam_i = 0 there and
+ *                   its equation is dropped, as in qpb_solve_backward.
+ *   status          a QP whose status is not QPB_OK gets zeros in every output
+ *                   and contributes exactly 0 to a sum, whatever its glam holds.
+ *   shared          qpb_solve_shared_backward's: a shared operand's gradient is
+ *                   ONE matrix, the sum over the batch; QPB_SHARED_A is ignored
+ *                   at m == 0.
+ *   required        H, x and gx; with m > 0 also A, lam and active.  status may
+ *                   be NULL (every QP counts as QPB_OK).
+ *   gH, gf, gA, gb  each may be NULL; at least one must be given.  With m == 0,
+ *                   gA and gb are ignored.
+ * Every element of every non-NULL output is written, and nothing else; a QP's
+ * per-QP outputs depend on its own inputs only; gH is symmetric bit for bit.
+ * With glam the kernels are the DU forms of qpb_solve_backward's
+ * (qpb_kkt_bwd.hip): glam_W goes to the rows' positions, R^T w = glam is one
+ * more substitution on the R the orthogonalisation left, Q w leaves the
+ * projected right-hand side and w joins the right-hand side of the R solve.
+ * Pass 2 and the workspace are qpb_solve_shared_backward's: the summed outputs'
+ * bits depend on the inputs and on (n, m, batch) only.
+ * Errors, in order: the descriptor as qpb_solve; flags != 0 and a bit of
+ * `shared` outside QPB_SHARED_H | QPB_SHARED_A QPB_ERR_INVALID_ARG; n > 32 or
+ * m > 64 QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are
+ * looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
+ * Follow-ups: the factored form (glam on a qpb_factor_shared_backward buffer);
+ * a glam for qpb_solve_box_backward, which there is a prescribed dx on the
+ * fixed variables; the n <= 128 Gram class.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_backward_dual(const qpb_desc *desc, int32_t shared,
+			    const double *H, const double *A, const double *x,
+			    const double *lam, const uint32_t *active,
+			    const int32_t *status, const double *gx,
+			    const double *glam, double *gH, double *gf,
+			    double *gA, double *gb, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (a shared operand and its
+ * gradient are one matrix). */
+int qpb_solve_backward_dual_host(const qpb_desc *desc, int32_t shared,
+				 const double *H, const double *A,
+				 const double *x, const double *lam,
+				 const uint32_t *active, const int32_t *status,
+				 const double *gx, const double *glam,
+				 double *gH, double *gf, double *gA,
+				 double *gb);
 
 /* Two-sided rows, the form OSQP and qpOASES state their constraints in:
  *   min 1/2 x^T H x + f^T x   s.t.   a_i x = bu_i            (rows i < meq; bl_i is not read)

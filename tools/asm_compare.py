@@ -12,7 +12,8 @@ that gained a trailing template parameter whose default is `false` (and a
 kernel that became such a template) is the same kernel under a longer name:
 it is found through its demangled name (c++filt, or $CXXFILT).  So is a kernel
 template that gained a trailing template parameter pack, empty in the old
-instantiations: another symbol with the same demangled name.  Kernels that
+instantiations: another symbol with the same demangled name (a second such
+pack behind a filled one only changes how c++filt spaces the closing `>`s).  Kernels that
 only NEW has are counted.  Exit status 1 when a kernel of OLD changed or is gone.
 """
 import os
@@ -28,7 +29,9 @@ def demangled(names):
     if not names:
         return {}
     out = subprocess.run([CXXFILT] + list(names), capture_output=True, text=True, check=True).stdout.splitlines()
-    return {n: re.sub(r"^void ", "", d) for n, d in zip(names, out)}
+    # (c++filt closes a nested template argument list as `> >` or `>>` depending on
+    # whether an empty pack follows it: one spelling)
+    return {n: re.sub(r"^void ", "", d).replace("> >", ">>") for n, d in zip(names, out)}
 
 
 def successor(name, old_dem, new_dem):
