@@ -570,6 +570,13 @@ extern "C" int qpb_solve_box_factored(const qpb_desc *d, const double *bxfac, co
       qpb::required(active, (m + 31) / 32), qpb::required(status, 1), qpb::optional(iters, 1));
 }
 
+// The two passes of qpb_solve_box_shared_backward (glam == NULL: its launches
+// and nothing else) and of qpb_solve_box_backward_dual on one H (glam given:
+// pass 1 is the SH DU forms), after the checks.  `what` names the call.
+static int box_shared_bwd_passes(const qpb_desc *d, const double *H, const double *x, const uint32_t *active,
+                                 const int32_t *status, const double *gx, const double *glam, double *gH, double *gf,
+                                 double *glb, double *gub, void *stream, const char *what);
+
 extern "C" int qpb_solve_box_shared_backward(const qpb_desc *d, const double *H, const double *x,
                                              const uint32_t *active, const int32_t *status, const double *gx,
                                              double *gH, double *gf, double *glb, double *gub, void *stream) {
@@ -583,22 +590,31 @@ extern "C" int qpb_solve_box_shared_backward(const qpb_desc *d, const double *H,
   if (rc) return rc;
   rc = check_device();
   if (rc) return rc;
-  const qpb::Route r = qpb::route_bwd_box_shared(d->n);
+  return box_shared_bwd_passes(d, H, x, active, status, gx, nullptr, gH, gf, glb, gub, stream, what);
+}
+
+static int box_shared_bwd_passes(const qpb_desc *d, const double *H, const double *x, const uint32_t *active,
+                                 const int32_t *status, const double *gx, const double *glam, double *gH, double *gf,
+                                 double *glb, double *gub, void *stream, const char *what) {
+  int rc = 0;
+  const qpb::Route r = qpb::route_bwd_box_dual(d->n);  // (route_bwd_box_shared's, with or without glam)
   const long long n = d->n, m = d->m, B = d->batch;
   const hipStream_t st = (hipStream_t)stream;
   // pass 1 over the batch in chunks, without gH: dx goes to gf1 (the caller's gf, or the workspace's)
   auto pass1 = [&](double *gf1) {
     return qpb::for_each_chunk(
         B, r.step,
-        [&](long long count, const double *xc, const uint32_t *ac, const int32_t *sc, const double *gxc, double *gfc,
-            double *glc, double *guc) {
+        [&](long long count, const double *xc, const uint32_t *ac, const int32_t *sc, const double *gxc,
+            const double *gmc, double *gfc, double *glc, double *guc) {
           qpb_desc c = *d;
           c.batch = count;
-          const hipError_t e = qpb_launch_kkt_bwd_box_shared(&c, 0LL, H, xc, ac, sc, gxc, nullptr, gfc, glc, guc, st);
-          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_box_shared_backward launch");
+          const hipError_t e =
+              glam ? qpb_launch_kkt_bwd_box_dual(&c, 0LL, H, xc, ac, sc, gxc, gmc, nullptr, gfc, glc, guc, st)
+                   : qpb_launch_kkt_bwd_box_shared(&c, 0LL, H, xc, ac, sc, gxc, nullptr, gfc, glc, guc, st);
+          return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
         },
         qpb::required(x, n), qpb::required(active, (m + 31) / 32), qpb::optional(status, 1), qpb::required(gx, n),
-        qpb::optional(gf1, n), qpb::optional(glb, n), qpb::optional(gub, n));
+        qpb::optional(glam, m), qpb::optional(gf1, n), qpb::optional(glb, n), qpb::optional(gub, n));
   };
   if (!gH) return pass1(gf);  // the sum is not wanted: pass 1 alone, no workspace
   // pass 2 is the batch sum of qpb_solve_shared_backward at m == 0: S = 1/2 sum (dx x^T + x dx^T) alone.
@@ -615,7 +631,57 @@ extern "C" int qpb_solve_box_shared_backward(const qpb_desc *d, const double *H,
     return qpb_launch_kkt_bwd_sum(&ds, x, dx, nullptr, nullptr, nullptr, status, slots, gH, nullptr, st);
   });
   if (rc) return rc;
-  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_box_shared_backward sum launch");
+  return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s sum launch: %s", what, hipGetErrorString(e));
+}
+
+// qpb_solve_box_backward_dual's argument rules after check_desc, up to the
+// pointers: check_bwd_box's, with the shared bit beside the flags
+static int check_bwd_box_dual(const qpb_desc *d, int32_t shared) {
+  static const char what[] = "qpb_solve_box_backward_dual";
+  if (d->m != 2 * d->n) return fail(QPB_ERR_INVALID_ARG, "%s: m must be 2n (got n=%d m=%d)", what, d->n, d->m);
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "%s: flags must be 0 (got %d)", what, d->flags);
+  if (shared & ~QPB_SHARED_H)
+    return fail(QPB_ERR_INVALID_ARG, "%s: shared must be 0 or QPB_SHARED_H (got %d)", what, shared);
+  if (qpb::route_bwd_box_dual(d->n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "%s: n=%d outside the backward box kernels (n<=%d)", what, d->n,
+                qpb::kBwdBoxDualMaxN);
+  return 0;
+}
+
+extern "C" int qpb_solve_box_backward_dual(const qpb_desc *d, int32_t shared, const double *H, const double *x,
+                                           const uint32_t *active, const int32_t *status, const double *gx,
+                                           const double *glam, double *gH, double *gf, double *glb, double *gub,
+                                           void *stream) {
+  static const char what[] = "qpb_solve_box_backward_dual";
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box_dual(d, shared);
+  if (rc) return rc;
+  // no cotangent on lam: the call is one of the two box backward calls, with their remaining rules
+  if (!glam)
+    return shared ? qpb_solve_box_shared_backward(d, H, x, active, status, gx, gH, gf, glb, gub, stream)
+                  : qpb_solve_box_backward(d, H, x, active, status, gx, gH, gf, glb, gub, stream);
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_arrays(H, x, active, gx, gH, gf, glb, gub, what);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  if (shared) return box_shared_bwd_passes(d, H, x, active, status, gx, glam, gH, gf, glb, gub, stream, what);
+  const qpb::Route r = qpb::route_bwd_box_dual(d->n);
+  const long long n = d->n, m = d->m;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const double *xc, const uint32_t *ac, const int32_t *sc,
+          const double *gxc, const double *gmc, double *gHc, double *gfc, double *glc, double *guc) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e =
+            qpb_launch_kkt_bwd_box_dual(&c, n * n, Hc, xc, ac, sc, gxc, gmc, gHc, gfc, glc, guc, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_box_backward_dual launch");
+      },
+      qpb::required(H, n * n), qpb::required(x, n), qpb::required(active, (m + 31) / 32), qpb::optional(status, 1),
+      qpb::required(gx, n), qpb::required(glam, m), qpb::optional(gH, n * n), qpb::optional(gf, n),
+      qpb::optional(glb, n), qpb::optional(gub, n));
 }
 
 extern "C" int qpb_solve_sections(const qpb_desc *d, const double *H, const double *f, const double *A,
@@ -924,43 +990,44 @@ extern "C" int qpb_factor_shared_backward(int32_t n, int32_t m, const double *H,
 }
 
 // qpb_solve_factored_backward's argument rules after check_desc, up to batch == 0
-static int check_factored_bwd(const qpb_desc *d) {
-  if (d->flags != 0)
-    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: flags must be 0 (got %d)", d->flags);
+// (and qpb_solve_factored_backward_dual's: `what` names the call)
+static int check_factored_bwd(const qpb_desc *d, const char *what = "qpb_solve_factored_backward") {
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "%s: flags must be 0 (got %d)", what, d->flags);
   if (qpb::route_factored_bwd(d->n, d->m).step == 0)
-    return fail(QPB_ERR_UNSUPPORTED,
-                "qpb_solve_factored_backward: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", d->n,
+    return fail(QPB_ERR_UNSUPPORTED, "%s: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", what, d->n,
                 d->m, qpb::kFactoredBwdMaxN, qpb::kFactoredBwdMaxM);
   return 0;
 }
 static int check_factored_bwd_arrays(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
                                      const uint32_t *active, const double *gx, const double *gH, const double *gf,
-                                     const double *gA, const double *gb) {
-  if (!bfac || !x || !gx) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: bfac, x and gx are required");
+                                     const double *gA, const double *gb,
+                                     const char *what = "qpb_solve_factored_backward") {
+  if (!bfac || !x || !gx) return fail(QPB_ERR_INVALID_ARG, "%s: bfac, x and gx are required", what);
   if (d->m > 0 && (!lam || !active))
-    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: lam and active are required when m > 0");
+    return fail(QPB_ERR_INVALID_ARG, "%s: lam and active are required when m > 0", what);
   if (!gH && !gf && !(d->m > 0 && (gA || gb)))
-    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: at least one of gH, gf, gA and gb is required");
+    return fail(QPB_ERR_INVALID_ARG, "%s: at least one of gH, gf, gA and gb is required", what);
   return 0;
 }
 
+// qpb_solve_factored_backward (glam == NULL: its launches and nothing else) and
+// qpb_solve_factored_backward_dual (glam given, m > 0: pass 1 is the DU forms).
 // qpb_solve_shared_backward's body with both operands shared and the factored
-// pass 1: the same chunk walk, workspace and pass 2
-extern "C" int qpb_solve_factored_backward(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
-                                           const uint32_t *active, const int32_t *status, const double *gx,
-                                           double *gH, double *gf, double *gA, double *gb, void *stream) {
+// pass 1: the same chunk walk, workspace and pass 2.  `what` names the call.
+static int factored_bwd(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
+                        const uint32_t *active, const int32_t *status, const double *gx, const double *glam,
+                        double *gH, double *gf, double *gA, double *gb, void *stream, const char *what) {
   int rc = check_desc(d);
   if (rc) return rc;
-  rc = check_factored_bwd(d);
+  rc = check_factored_bwd(d, what);
   if (rc) return rc;
   if (d->batch == 0) return 0;
-  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb);
+  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb, what);
   if (rc) return rc;
-  if ((uintptr_t)bfac & 15)
-    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_factored_backward: bfac must be 16-byte aligned");
+  if ((uintptr_t)bfac & 15) return fail(QPB_ERR_INVALID_ARG, "%s: bfac must be 16-byte aligned", what);
   rc = check_device();
   if (rc) return rc;
-  const qpb::Route r = qpb::route_factored_bwd(d->n, d->m);
+  const qpb::Route r = qpb::route_factored_bwd_dual(d->n, d->m);  // (route_factored_bwd's, with or without glam)
   const long long n = d->n, m = d->m, B = d->batch;
   if (m == 0) gA = gb = nullptr;  // ignored
   const hipStream_t st = (hipStream_t)stream;
@@ -970,14 +1037,16 @@ extern "C" int qpb_solve_factored_backward(const qpb_desc *d, const double *bfac
     return qpb::for_each_chunk(
         B, r.step,
         [&](long long count, const double *Fc, const double *xc, const double *lc, const uint32_t *ac,
-            const int32_t *sc, const double *gxc, double *gfc, double *gbc) {
+            const int32_t *sc, const double *gxc, const double *glc, double *gfc, double *gbc) {
           qpb_desc c = *d;
           c.batch = count;
-          const hipError_t e = qpb_launch_kkt_bwd_factored(&c, Fc, xc, lc, ac, sc, gxc, gfc, gbc, st);
-          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_factored_backward launch");
+          const hipError_t e = glam ? qpb_launch_kkt_bwd_factored_dual(&c, Fc, xc, lc, ac, sc, gxc, glc, gfc, gbc, st)
+                                    : qpb_launch_kkt_bwd_factored(&c, Fc, xc, lc, ac, sc, gxc, gfc, gbc, st);
+          return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
         },
         qpb::required(bfac, 0), qpb::required(x, n), qpb::optional(lam, m), qpb::optional(active, (m + 31) / 32),
-        qpb::optional(status, 1), qpb::required(gx, n), qpb::optional(gf1, n), qpb::optional(gb1, m));
+        qpb::optional(status, 1), qpb::required(gx, n), qpb::optional(glam, m), qpb::optional(gf1, n),
+        qpb::optional(gb1, m));
   };
   if (!gH && !gA) return pass1(gf, gb);  // the summed gradients are not wanted: pass 1 alone
   // workspace, as qpb_solve_shared_backward's: the slots, then dx (B n) where gf
@@ -993,7 +1062,25 @@ extern "C" int qpb_solve_factored_backward(const qpb_desc *d, const double *bfac
     return qpb_launch_kkt_bwd_sum(d, x, dx, gbs, lam, active, status, slots, gH, gA, st);
   });
   if (rc) return rc;
-  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_factored_backward sum launch");
+  return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s sum launch: %s", what, hipGetErrorString(e));
+}
+
+extern "C" int qpb_solve_factored_backward(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
+                                           const uint32_t *active, const int32_t *status, const double *gx,
+                                           double *gH, double *gf, double *gA, double *gb, void *stream) {
+  return factored_bwd(d, bfac, x, lam, active, status, gx, nullptr, gH, gf, gA, gb, stream,
+                      "qpb_solve_factored_backward");
+}
+
+extern "C" int qpb_solve_factored_backward_dual(const qpb_desc *d, const double *bfac, const double *x,
+                                                const double *lam, const uint32_t *active, const int32_t *status,
+                                                const double *gx, const double *glam, double *gH, double *gf,
+                                                double *gA, double *gb, void *stream) {
+  // no cotangent on lam: the call is qpb_solve_factored_backward
+  if (!glam || (d && d->m == 0))
+    return qpb_solve_factored_backward(d, bfac, x, lam, active, status, gx, gH, gf, gA, gb, stream);
+  return factored_bwd(d, bfac, x, lam, active, status, gx, glam, gH, gf, gA, gb, stream,
+                      "qpb_solve_factored_backward_dual");
 }
 
 extern "C" int qpb_factor_shared_backward_host(int32_t n, int32_t m, const double *H, const double *A, double *bfac,
@@ -1016,40 +1103,59 @@ extern "C" int qpb_factor_shared_backward_host(int32_t n, int32_t m, const doubl
   return 0;
 }
 
-extern "C" int qpb_solve_factored_backward_host(const qpb_desc *d, const double *bfac, const double *x,
-                                                const double *lam, const uint32_t *active, const int32_t *status,
-                                                const double *gx, double *gH, double *gf, double *gA, double *gb) {
+// qpb_solve_factored_backward_host and qpb_solve_factored_backward_dual_host
+// (glam, may be NULL): copy in, run, copy out
+static int factored_bwd_host(const qpb_desc *d, const double *bfac, const double *x, const double *lam,
+                             const uint32_t *active, const int32_t *status, const double *gx, const double *glam,
+                             double *gH, double *gf, double *gA, double *gb, const char *what) {
   int rc = check_desc(d);
   if (rc) return rc;
-  rc = check_factored_bwd(d);
+  rc = check_factored_bwd(d, what);
   if (rc) return rc;
   if (d->batch == 0) return 0;
-  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb);  // host pointers: the same rules
+  rc = check_factored_bwd_arrays(d, bfac, x, lam, active, gx, gH, gf, gA, gb, what);  // host pointers: the same rules
   if (rc) return rc;
   rc = check_device();
   if (rc) return rc;
   const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32;
-  DevBuf dF, dx, dl, da, ds, dg, oH, of, oA, ob;
+  DevBuf dF, dx, dl, da, ds, dg, dgl, oH, of, oA, ob;
   HIPCHK(up(dF, bfac, (size_t)qpb::bfct::layout(d->n, d->m).size * 8), "bfac");
   HIPCHK(up(dx, x, B * n * 8), "x");
   HIPCHK(up(dl, m ? lam : nullptr, B * m * 8), "lam");
   HIPCHK(up(da, m ? active : nullptr, B * w * 4), "active");
   HIPCHK(up(ds, status, B * 4), "status");
   HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(up(dgl, m ? glam : nullptr, B * m * 8), "glam");
   HIPCHK(alloc(oH, gH, n * n * 8), "gH");
   HIPCHK(alloc(of, gf, B * n * 8), "gf");
   HIPCHK(alloc(oA, m ? gA : nullptr, m * n * 8), "gA");
   HIPCHK(alloc(ob, m ? gb : nullptr, B * m * 8), "gb");
-  rc = qpb_solve_factored_backward(d, (double *)dF.p, (double *)dx.p, (double *)dl.p, (uint32_t *)da.p,
-                                   (int32_t *)ds.p, (double *)dg.p, (double *)oH.p, (double *)of.p, (double *)oA.p,
-                                   (double *)ob.p, nullptr);
+  rc = qpb_solve_factored_backward_dual(d, (double *)dF.p, (double *)dx.p, (double *)dl.p, (uint32_t *)da.p,
+                                        (int32_t *)ds.p, (double *)dg.p, (double *)dgl.p, (double *)oH.p,
+                                        (double *)of.p, (double *)oA.p, (double *)ob.p, nullptr);
   if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize(), "qpb_solve_factored_backward_host kernel");
+  if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
+    return fail(QPB_ERR_HIP, "%s_host kernel: %s", what, hipGetErrorString(e));
   HIPCHK(down(gH, oH, n * n * 8), "gH D2H");
   HIPCHK(down(gf, of, B * n * 8), "gf D2H");
   HIPCHK(down(m ? gA : nullptr, oA, m * n * 8), "gA D2H");
   HIPCHK(down(m ? gb : nullptr, ob, B * m * 8), "gb D2H");
   return 0;
+}
+
+extern "C" int qpb_solve_factored_backward_host(const qpb_desc *d, const double *bfac, const double *x,
+                                                const double *lam, const uint32_t *active, const int32_t *status,
+                                                const double *gx, double *gH, double *gf, double *gA, double *gb) {
+  return factored_bwd_host(d, bfac, x, lam, active, status, gx, nullptr, gH, gf, gA, gb,
+                           "qpb_solve_factored_backward");
+}
+
+extern "C" int qpb_solve_factored_backward_dual_host(const qpb_desc *d, const double *bfac, const double *x,
+                                                     const double *lam, const uint32_t *active,
+                                                     const int32_t *status, const double *gx, const double *glam,
+                                                     double *gH, double *gf, double *gA, double *gb) {
+  return factored_bwd_host(d, bfac, x, lam, active, status, gx, glam, gH, gf, gA, gb,
+                           glam ? "qpb_solve_factored_backward_dual" : "qpb_solve_factored_backward");
 }
 
 // ---- two-sided rows bl <= A x <= bu -------------------------------------------
@@ -1353,6 +1459,44 @@ extern "C" int qpb_solve_box_backward_host(const qpb_desc *d, const double *H, c
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "qpb_solve_box_backward_host kernel");
   HIPCHK(down(gH, oH, B * n * n * 8), "gH D2H");
+  HIPCHK(down(gf, of, B * n * 8), "gf D2H");
+  HIPCHK(down(glb, ol, B * n * 8), "glb D2H");
+  HIPCHK(down(gub, ou, B * n * 8), "gub D2H");
+  return 0;
+}
+
+extern "C" int qpb_solve_box_backward_dual_host(const qpb_desc *d, int32_t shared, const double *H, const double *x,
+                                                const uint32_t *active, const int32_t *status, const double *gx,
+                                                const double *glam, double *gH, double *gf, double *glb,
+                                                double *gub) {
+  static const char what[] = "qpb_solve_box_backward_dual";
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box_dual(d, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_arrays(H, x, active, gx, gH, gf, glb, gub, what);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, w = (2 * n + 31) / 32, BH = shared ? 1 : B;
+  DevBuf dH, dx, da, ds, dg, dgl, oH, of, ol, ou;
+  HIPCHK(up(dH, H, BH * n * n * 8), "H");
+  HIPCHK(up(dx, x, B * n * 8), "x");
+  HIPCHK(up(da, active, B * w * 4), "active");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(up(dgl, glam, B * 2 * n * 8), "glam");
+  HIPCHK(alloc(oH, gH, BH * n * n * 8), "gH");
+  HIPCHK(alloc(of, gf, B * n * 8), "gf");
+  HIPCHK(alloc(ol, glb, B * n * 8), "glb");
+  HIPCHK(alloc(ou, gub, B * n * 8), "gub");
+  rc = qpb_solve_box_backward_dual(d, shared, (double *)dH.p, (double *)dx.p, (uint32_t *)da.p, (int32_t *)ds.p,
+                                   (double *)dg.p, (double *)dgl.p, (double *)oH.p, (double *)of.p, (double *)ol.p,
+                                   (double *)ou.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_box_backward_dual_host kernel");
+  HIPCHK(down(gH, oH, BH * n * n * 8), "gH D2H");
   HIPCHK(down(gf, of, B * n * 8), "gf D2H");
   HIPCHK(down(glb, ol, B * n * 8), "glb D2H");
   HIPCHK(down(gub, ou, B * n * 8), "gub D2H");

@@ -104,7 +104,9 @@ using Form = std::integral_constant<int, FM>;
 // scattered to the rows' positions (g), R^T w = g is solved on R's columns,
 // Q w leaves z after the two projection passes and w joins the right-hand side
 // of the R solve.  Deduced from the launch's trailing argument; the other
-// forms have no such argument and none of this code.
+// forms have no such argument and none of this code.  On a buffer (FM == 2,
+// qpb_solve_factored_backward_dual) the four steps are the same code behind the
+// factored load: R and Q are per QP, from the orthogonalisation, either way.
 template <int MR, bool N16, bool SH = false, class... FMP, class... GL>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
@@ -114,8 +116,8 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   constexpr bool DU = sizeof...(GL) == 1;
-  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM != 0),
-                "glam is one array, beside H and A");
+  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM == 1),
+                "glam is one array, beside H and A or a buffer of them");
   __shared__ double lds[QPB * SLOT];
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -610,8 +612,8 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   constexpr bool DU = sizeof...(GL) == 1;
-  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM != 0),
-                "glam is one array, beside H and A");
+  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM == 1),
+                "glam is one array, beside H and A or a buffer of them");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -1000,6 +1002,28 @@ extern "C" hipError_t qpb_launch_kkt_bwd_factored(const qpb_desc *d, const doubl
     hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, qpb::bwd::Form<2>>), dim3((unsigned)blocks), dim3(64), 0,
                        stream, bfac, no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m,
                        (long long)d->batch);
+  });
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_factored_backward_dual (m > 0 and glam given): the DU
+// forms of the factored forms
+extern "C" hipError_t qpb_launch_kkt_bwd_factored_dual(const qpb_desc *d, const double *bfac, const double *x,
+                                                       const double *lam, const uint32_t *active,
+                                                       const int32_t *status, const double *gx, const double *glam,
+                                                       double *gf, double *gb, hipStream_t stream) {
+  const double *no_a = nullptr;
+  double *no_o = nullptr;
+  if (d->n > 16 || d->m > 32) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_wave_kernel<false, qpb::bwd::Form<2>>), dim3((unsigned)d->batch), dim3(64), 0, stream, bfac,
+                       no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m, (long long)d->batch, glam);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, qpb::bwd::Form<2>>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, bfac, no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m,
+                       (long long)d->batch, glam);
   });
   return hipGetLastError();
 }

@@ -58,16 +58,37 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
 // changes, so gf, glb and gub are the other form's bit for bit.  The form's
 // gHg is per QP like the other's (pass 1 passes NULL: the sum is pass 2's).
 // Without SH the pack is empty: the signatures and code objects stay.
-template <bool SH, class... STR>
-inline constexpr bool stride_pack_ok = sizeof...(STR) == (SH ? 1 : 0) && (std::is_same_v<STR, long long> && ...);
+// DU (qpb_solve_box_backward_dual, both kernels, plain and SH): the cotangent
+// glam on the multipliers, B x 2n in qpb_solve_box's lam layout (the upper
+// bounds' entries, then the lower bounds'), is the pack's last argument, a
+// const double *, which only this form has.  On unit rows it prescribes dx on
+// the fixed variables: d_j = -glam[j] where the upper bit of j is set,
+// +glam[n + j] where only the lower bit is, 0 on a free variable, and
+//
+//     dx_S = d_S                   H_FF dx_F = -g_F - H_FS d_S
+//
+// with r, and every output's formula, as above.  The masked Cholesky is the
+// same; the new work is d, one product of the untouched rows of H with it, and
+// d on the fixed lanes where the other forms store zeros.
+template <bool SH, class... EX>
+inline constexpr bool extra_pack_ok =
+    SH ? (std::is_same_v<void(EX...), void(long long)> || std::is_same_v<void(EX...), void(long long, const double *)>)
+       : (std::is_same_v<void(EX...), void()> || std::is_same_v<void(EX...), void(const double *)>);
+template <class... T>
+__device__ __forceinline__ long long pack_stride(long long s, T...) {
+  return s;
+}
+__device__ __forceinline__ const double *pack_glam(const double *p) { return p; }
+__device__ __forceinline__ const double *pack_glam(long long, const double *p) { return p; }
 
-template <bool N16, bool SH = false, class... STR>
+template <bool N16, bool SH = false, class... EX>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
     double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
-    STR... strideH) {
-  static_assert(stride_pack_ok<SH, STR...>, "the shared form alone takes the stride");
+    EX... extra) {
+  static_assert(extra_pack_ok<SH, EX...>, "the shared form alone takes the stride, the dual form glam behind it");
+  constexpr bool DU = sizeof...(EX) == (SH ? 2 : 1);
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -82,7 +103,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   const int lc = var ? l : n - 1;
   const double *Hq;
   if constexpr (SH)
-    Hq = Hg + g * (strideH + ...);
+    Hq = Hg + g * pack_stride(extra...);
   else
     Hq = Hg + g * (long long)n * n;
   const bool ok = statg ? statg[g] == QPB_OK : true;
@@ -92,6 +113,15 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   const uint32_t fixed = (W | (W >> n)) & nmask;
   const double gv = gxg[g * n + lc];
   const double xv = xg[g * n + lc];
+  [[maybe_unused]] double dv = 0.0;  // DU: the prescribed dx of a fixed variable, 0 on a free or padded one
+  if constexpr (DU) {
+    // both entries are loaded and one is selected: whatever glam holds at a
+    // clear bit, NaN included, goes nowhere
+    const double *__restrict__ glq = pack_glam(extra...) + g * (long long)(2 * n);
+    const double gu = glq[lc], gw = glq[n + lc];
+    const bool bu = var && ((W >> l) & 1u), bl = var && ((W >> (l + n)) & 1u);
+    dv = bu ? -gu : (bl ? gw : 0.0);
+  }
   double Hr[NL];  // row l of H, untouched
   if constexpr (N16) {
     // coalesced 16-byte loads, two whole rows of each of the wave's 4 QPs per
@@ -146,8 +176,20 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   store_l(Lp, l, Lr);  // for the second solve
 
   // ---- dx = -H~^{-1} g~: exact zeros on the fixed lanes
-  double dx = solve_x(fix ? 0.0 : gv, invLd, Lr, Lp, l, xcap);
+  double rhs = gv;
+  if constexpr (DU) {
+    // g_F + H_FS d_S: d is zero off S, so the whole untouched row serves; d_k
+    // is read from lane k by the FMA, as dx is for r below
+    pin(dv);
+    dpp_ready(dv);
+    unroll<NL>([&](auto K) { fmac_bc<K>(rhs, dv, Hr[K]); });
+  }
+  double dx = solve_x(fix ? 0.0 : rhs, invLd, Lr, Lp, l, xcap);
   if (fix || !ok) dx = 0.0;
+  // (DU: the fixed lanes' identity rows would carry d through the two solves
+  // times 1 / sqrt(1) twice; the select keeps dx_S = d_S to the bit whatever
+  // that rounds to.  d is 0 on a QP that is not QPB_OK: it has no fixed variable)
+  if constexpr (DU) dx = fix ? dv : dx;
   // ---- r = g + H dx from the untouched row, dx_k read from lane k by the FMA
   double r = gv;
   pin(dx);
@@ -206,13 +248,14 @@ constexpr int W_L = 0, W_H = WN * WS, W_X = 2 * WN * WS, W_DX = W_X + 32, W_SIZE
 constexpr int W_COL = WN + 2;  // the pivot column of a factorisation step, zero past the matrix
 static_assert((W_SIZE + W_COL) * 8 <= 20480, "8 waves per CU by LDS");
 
-template <bool SH = false, class... STR>
+template <bool SH = false, class... EX>
 __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
     const double *__restrict__ Hg, const double *__restrict__ xg, const uint32_t *__restrict__ actg,
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
     double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
-    STR... strideH) {
-  static_assert(stride_pack_ok<SH, STR...>, "the shared form alone takes the stride");
+    EX... extra) {
+  static_assert(extra_pack_ok<SH, EX...>, "the shared form alone takes the stride, the dual form glam behind it");
+  constexpr bool DU = sizeof...(EX) == (SH ? 2 : 1);
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -224,7 +267,7 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
   double *Lm = lds + W_L, *Hm = lds + W_H, *X = lds + W_X, *DX = lds + W_DX;
   const double *Hq;
   if constexpr (SH)
-    Hq = Hg + g * (strideH + ...);
+    Hq = Hg + g * pack_stride(extra...);
   else
     Hq = Hg + g * (long long)n * n;
   const bool ok = statg ? statg[g] == QPB_OK : true;
@@ -253,9 +296,33 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
   const bool var = lane < n;
   const bool fix = !var || ((fixed >> i) & 1u);  // (lane < n <= 32: i == lane)
   const double gv = var ? gxg[g * n + lane] : 0.0;
+  [[maybe_unused]] double dv = 0.0;  // DU: the prescribed dx of a fixed variable, 0 on a free or padded one
+  if constexpr (DU) {
+    // both entries are loaded and one is selected: whatever glam holds at a
+    // clear bit, NaN included, goes nowhere
+    const double *__restrict__ glq = pack_glam(extra...) + g * (long long)(2 * n);
+    const int lc = var ? lane : 0;
+    const double gu = glq[lc], gw = glq[n + lc];
+    const bool bu = var && ((upw >> i) & 1u), bl = var && ((low_w >> i) & 1u);
+    dv = bu ? -gu : (bl ? gw : 0.0);
+    if (low) DX[lane] = dv;
+  }
   double ui = fix ? 0.0 : gv;       // the running g~, u_k = (L^{-1} g~)_k from step k on
   double invLd = var ? 0.0 : 1.0;   // 1 / L[lane][lane] (1 on the padding)
   wave_lds_sync();
+  if constexpr (DU) {
+    // g~_F = g_F + H_FS d_S: d is zero off S, so the whole untouched row
+    // serves, by the loop of r below
+    if (!fix) {
+      double r0 = gv, r1 = 0.0;
+#pragma unroll
+      for (int j = 0; j < WN; j += 2) {
+        r0 = __builtin_fma(Hm[lane * WS + j], DX[j], r0);
+        r1 = __builtin_fma(Hm[lane * WS + j + 1], DX[j + 1], r1);
+      }
+      ui = r0 + r1;
+    }
+  }
 
   // ---- H~ = L L^T (right-looking, in place) and u = L^{-1} g~: kkt_bwd_wave_kernel's
   // loop.  Step k updates the whole rows k+1.. of the symmetric trailing
@@ -295,6 +362,9 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
     dx = lane == j ? dj : __builtin_fma(-lj, dj, dx);
   }
   if (!ok || fix) dx = 0.0;
+  // (DU: dx_S = d_S to the bit; d is 0 on the padding and on a QP that is not
+  // QPB_OK, which has no fixed variable)
+  if constexpr (DU) dx = fix ? dv : dx;
   if (low) {
     X[lane] = (ok && var) ? xg[g * n + lane] : 0.0;
     DX[lane] = dx;
@@ -365,5 +435,38 @@ extern "C" hipError_t qpb_launch_kkt_bwd_box_shared(const qpb_desc *d, long long
   else
     hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<false, true, long long>), dim3((unsigned)blocks), dim3(64), 0, stream,
                        H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, strideH);
+  return hipGetLastError();
+}
+
+// qpb_solve_box_backward_dual with glam given: the DU forms, plain where H is
+// batched (strideH == n n) and SH on one H for the batch (strideH == 0, pass 1
+// of the shared form: gH NULL, the sum is pass 2's)
+extern "C" hipError_t qpb_launch_kkt_bwd_box_dual(const qpb_desc *d, long long strideH, const double *H,
+                                                  const double *x, const uint32_t *active, const int32_t *status,
+                                                  const double *gx, const double *glam, double *gH, double *gf,
+                                                  double *glb, double *gub, hipStream_t stream) {
+  using namespace qpb::bwdbox;
+  const bool sh = strideH == 0;
+  const long long blocks = (d->batch + QPB - 1) / QPB;
+  if (d->n > 16 && sh)
+    hipLaunchKernelGGL((kkt_bwd_box_wave_kernel<true, long long, const double *>), dim3((unsigned)d->batch), dim3(64),
+                       0, stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, strideH, glam);
+  else if (d->n > 16)
+    hipLaunchKernelGGL((kkt_bwd_box_wave_kernel<false, const double *>), dim3((unsigned)d->batch), dim3(64), 0, stream,
+                       H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, glam);
+  else if (d->n == 16 && sh)
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<true, true, long long, const double *>), dim3((unsigned)blocks),
+                       dim3(64), 0, stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch,
+                       strideH, glam);
+  else if (d->n == 16)
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<true, false, const double *>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, glam);
+  else if (sh)
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<false, true, long long, const double *>), dim3((unsigned)blocks),
+                       dim3(64), 0, stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch,
+                       strideH, glam);
+  else
+    hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<false, false, const double *>), dim3((unsigned)blocks), dim3(64), 0,
+                       stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, glam);
   return hipGetLastError();
 }

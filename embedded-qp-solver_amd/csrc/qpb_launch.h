@@ -137,6 +137,19 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factor(int n, int m, const double *H,
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factored(const qpb_desc *d, const double *bfac, const double *x,
                                                     const double *lam, const uint32_t *active, const int32_t *status,
                                                     const double *gx, double *gf, double *gb, hipStream_t stream);
+// qpb_solve_factored_backward_dual, pass 1 (d->m > 0, glam not NULL): the DU
+// forms of those factored forms, with glam (B x m) as the lower right-hand side
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factored_dual(const qpb_desc *d, const double *bfac, const double *x,
+                                                         const double *lam, const uint32_t *active,
+                                                         const int32_t *status, const double *gx, const double *glam,
+                                                         double *gf, double *gb, hipStream_t stream);
+// qpb_solve_box_backward_dual (glam not NULL, B x 2n): the DU forms of
+// qpb_launch_kkt_bwd_box (strideH == n n) and of qpb_launch_kkt_bwd_box_shared
+// (strideH == 0: pass 1, gH NULL)
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box_dual(const qpb_desc *d, long long strideH, const double *H,
+                                                    const double *x, const uint32_t *active, const int32_t *status,
+                                                    const double *gx, const double *glam, double *gH, double *gf,
+                                                    double *glb, double *gub, hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

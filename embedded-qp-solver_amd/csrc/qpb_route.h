@@ -277,6 +277,56 @@ static_assert(route_factored_bwd(16, 32).kernel == route_factored(16, 32).kernel
               route_factored_bwd(17, 0).kernel == route_factored(17, 0).kernel &&
               kFactoredBwdMaxN == kFactoredMaxN && kFactoredBwdMaxM == kFactoredMaxM);
 
+// qpb_solve_factored_backward_dual: route_factored_bwd's classes, whose DU forms
+// of the factored forms take glam on the same buffer; above them there is
+// none: step 0, and the call is unsupported.
+constexpr Route route_factored_bwd_dual(int n, int m) {
+  const Route r = route_factored_bwd(n, m);
+  return {r.kernel, r.step};
+}
+constexpr int kFactoredBwdDualMaxN = kFactoredBwdMaxN, kFactoredBwdDualMaxM = kFactoredBwdMaxM;
+
+static_assert(route_factored_bwd_dual(1, 0).kernel == Kernel::gi_dense &&
+              route_factored_bwd_dual(16, 32).kernel == Kernel::gi_dense);
+static_assert(route_factored_bwd_dual(16, 33).kernel == Kernel::gi_wave &&
+              route_factored_bwd_dual(17, 0).kernel == Kernel::gi_wave &&
+              route_factored_bwd_dual(32, 64).kernel == Kernel::gi_wave);
+// the buffer is the factored backward's and the bits are the unfactored dual call's: both classes and steps
+static_assert(route_factored_bwd_dual(16, 32).kernel == route_factored_bwd(16, 32).kernel &&
+              route_factored_bwd_dual(16, 32).step == route_factored_bwd(16, 32).step &&
+              route_factored_bwd_dual(32, 64).kernel == route_factored_bwd(32, 64).kernel &&
+              route_factored_bwd_dual(32, 64).step == route_factored_bwd(32, 64).step);
+static_assert(route_factored_bwd_dual(16, 32).kernel == route_bwd_dual(16, 32).kernel &&
+              route_factored_bwd_dual(16, 33).kernel == route_bwd_dual(16, 33).kernel &&
+              route_factored_bwd_dual(17, 0).kernel == route_bwd_dual(17, 0).kernel &&
+              route_factored_bwd_dual(16, 32).step == route_bwd_dual(16, 32).step &&
+              route_factored_bwd_dual(32, 64).step == route_bwd_dual(32, 64).step);
+static_assert(route_factored_bwd_dual(33, 0).step == 0 && route_factored_bwd_dual(16, 65).step == 0 &&
+              route_factored_bwd_dual(128, 256).step == 0);
+static_assert(route_factored_bwd_dual(kFactoredBwdDualMaxN, kFactoredBwdDualMaxM).step > 0 &&
+              route_factored_bwd_dual(kFactoredBwdDualMaxN + 1, 1).step == 0 &&
+              route_factored_bwd_dual(1, kFactoredBwdDualMaxM + 1).step == 0);
+static_assert(kFactoredBwdDualMaxN == kBwdDualMaxN && kFactoredBwdDualMaxM == kBwdDualMaxM);
+
+// qpb_solve_box_backward_dual, batched H or one H: route_bwd_box's classes,
+// whose DU forms (plain and SH) take glam; above them there is none: step 0,
+// and the call is unsupported.
+constexpr Route route_bwd_box_dual(int n) { return route_bwd_box(n); }
+constexpr int kBwdBoxDualMaxN = kBwdBoxMaxN;
+
+static_assert(route_bwd_box_dual(1).kernel == Kernel::gi_box && route_bwd_box_dual(16).kernel == Kernel::gi_box);
+static_assert(route_bwd_box_dual(17).kernel == Kernel::gi_wave_box &&
+              route_bwd_box_dual(32).kernel == Kernel::gi_wave_box);
+static_assert(route_bwd_box_dual(16).kernel == route_bwd_box_shared(16).kernel &&
+              route_bwd_box_dual(16).step == route_bwd_box_shared(16).step &&
+              route_bwd_box_dual(32).kernel == route_bwd_box_shared(32).kernel &&
+              route_bwd_box_dual(32).step == route_bwd_box_shared(32).step);
+static_assert(route_bwd_box_dual(33).step == 0 && route_bwd_box_dual(128).step == 0);
+static_assert(route_bwd_box_dual(kBwdBoxDualMaxN).step > 0 && route_bwd_box_dual(kBwdBoxDualMaxN + 1).step == 0);
+// a box solve's outputs go to it unchanged: the forward's classes
+static_assert(route_bwd_box_dual(16).kernel == route(16, 32, 0, true).kernel &&
+              route_bwd_box_dual(17).kernel == route(17, 34, 0, true).kernel);
+
 // qpb_solve_range with m > 0: the RG forms of the two wavefront-level classes,
 // whatever meq and the shared bits (the forms take both at run time); above
 // them -- the Gram class -- there is no range form yet: step 0, and the call is

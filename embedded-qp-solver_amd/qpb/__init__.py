@@ -116,6 +116,10 @@ _lib.qpb_solve_factored_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
 _lib.qpb_solve_factored_backward.restype = ctypes.c_int
 _lib.qpb_solve_factored_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 10
 _lib.qpb_solve_factored_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward_dual.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 12
+_lib.qpb_solve_factored_backward_dual.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward_dual_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 11
+_lib.qpb_solve_factored_backward_dual_host.restype = ctypes.c_int
 _lib.qpb_solve_range.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 12
 _lib.qpb_solve_range.restype = ctypes.c_int
 _lib.qpb_solve_range_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 11
@@ -138,6 +142,10 @@ _lib.qpb_solve_box_shared_backward.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 1
 _lib.qpb_solve_box_shared_backward.restype = ctypes.c_int
 _lib.qpb_solve_box_shared_backward_host.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 9
 _lib.qpb_solve_box_shared_backward_host.restype = ctypes.c_int
+_lib.qpb_solve_box_backward_dual.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
+_lib.qpb_solve_box_backward_dual.restype = ctypes.c_int
+_lib.qpb_solve_box_backward_dual_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
+_lib.qpb_solve_box_backward_dual_host.restype = ctypes.c_int
 _lib.qpb_factor_box_doubles.argtypes = [ctypes.c_int32]
 _lib.qpb_factor_box_doubles.restype = ctypes.c_int64
 _lib.qpb_factor_box.argtypes = [ctypes.c_int32] + [_vp] * 4
@@ -965,9 +973,24 @@ def solve_factored_backward(F: BackwardFactor, sol: Solution, gx, *, need=NEED_A
     gb (B, m)), each bit for bit what ``solve_shared_backward(H, A, sol, gx)``
     returns; an entry is None where ``need`` leaves it out, and gA and gb with
     m == 0."""
+    return _solve_factored_backward("solve_factored_backward", F, sol, gx, None, need, stream)
+
+
+def solve_factored_backward_dual(F: BackwardFactor, sol: Solution, gx, glam, *, need=NEED_ALL, stream=None):
+    """``solve_backward_dual`` with a 2-D H and A on a backward factor buffer
+    (qpb_solve_factored_backward_dual): ``solve_factored_backward`` for a loss
+    that also reads the multipliers, ``glam = dl/dlam`` (B, m) in ``sol.lam``'s
+    layout and sign convention.  Every output is bit for bit what
+    ``solve_backward_dual(H, A, sol, gx, glam)`` returns for the 2-D H and A that
+    ``F`` was made from.  ``glam=None`` (or m = 0) is ``solve_factored_backward``,
+    bit for bit."""
+    return _solve_factored_backward("solve_factored_backward_dual", F, sol, gx, glam, need, stream)
+
+
+def _solve_factored_backward(who: str, F: BackwardFactor, sol: Solution, gx, glam, need, stream):
     import torch
     if not (gx.is_cuda and F.fac.is_cuda):
-        raise ValueError("qpb.solve_factored_backward expects CUDA (HIP) tensors; use solve_factored_backward_host "
+        raise ValueError(f"qpb.{who} expects CUDA (HIP) tensors; use {who}_host "
                          "for numpy")
     n, m = int(F.n), int(F.m)
     need = _need_set(need)
@@ -992,6 +1015,9 @@ def solve_factored_backward(F: BackwardFactor, sol: Solution, gx, *, need=NEED_A
     if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
                                    or sol.status.shape != (B,)):
         raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    if glam is not None and (not glam.is_cuda or glam.dtype != torch.float64 or not glam.is_contiguous()
+                             or glam.device != gx.device or tuple(glam.shape) != (B, m)):
+        raise ValueError("glam must be a contiguous float64 CUDA tensor of shape (B, m) on gx's device, or None")
     dev = gx.device
     new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
     gH = new(n, n) if "H" in need else None
@@ -1001,11 +1027,36 @@ def solve_factored_backward(F: BackwardFactor, sol: Solution, gx, *, need=NEED_A
     if gH is None and gf is None and gA is None and gb is None:
         return None, None, None, None  # m == 0 and only A / b wanted
     d = Desc(n, m, B, 0, 0, 0.0)
-    rc = _lib.qpb_solve_factored_backward(ctypes.byref(d), _ptr(F.fac), _ptr(sol.x), _ptr(sol.lam) if m else None,
-                                          _ptr(sol.active) if m else None, _ptr(sol.status), _ptr(gx), _ptr(gH),
-                                          _ptr(gf), _ptr(gA), _ptr(gb), _stream_ptr(stream))
-    _check(rc, "qpb_solve_factored_backward")
+    if glam is None or not m:
+        rc = _lib.qpb_solve_factored_backward(ctypes.byref(d), _ptr(F.fac), _ptr(sol.x), _ptr(sol.lam) if m else None,
+                                              _ptr(sol.active) if m else None, _ptr(sol.status), _ptr(gx), _ptr(gH),
+                                              _ptr(gf), _ptr(gA), _ptr(gb), _stream_ptr(stream))
+        _check(rc, "qpb_solve_factored_backward")
+    else:
+        rc = _lib.qpb_solve_factored_backward_dual(ctypes.byref(d), _ptr(F.fac), _ptr(sol.x), _ptr(sol.lam),
+                                                   _ptr(sol.active), _ptr(sol.status), _ptr(gx), _ptr(glam), _ptr(gH),
+                                                   _ptr(gf), _ptr(gA), _ptr(gb), _stream_ptr(stream))
+        _check(rc, "qpb_solve_factored_backward_dual")
     return gH, gf, gA, gb
+
+
+def solve_factored_tangent(F: BackwardFactor, sol: Solution, df, db=None, *, stream=None):
+    """``solve_tangent`` on a backward factor buffer: the tangent ``(dx, dlam)``
+    of (x*, lam*) along ``df`` (B, n) and ``db`` (B, m) at fixed active set,
+    without H and A and without the per-QP set-up -- ONE call of
+    ``solve_factored_backward_dual`` with ``gx = df``, ``glam = -db`` and
+    ``need = ("f", "b")``.  Bit for bit ``solve_tangent(H, A, sol, df, db)`` on
+    the 2-D H and A that ``F`` was made from.  For an MPC loop that factors its
+    plant model once, this is the local affine law around a tick's solution at
+    the factored path's cost."""
+    import contextlib
+
+    import torch
+    m = int(F.m)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        glam = None if db is None or not m else -db
+        _, dx, _, gb = solve_factored_backward_dual(F, sol, df, glam, need=("f", "b"), stream=stream)
+        return dx, (None if gb is None else -gb)
 
 
 def factor_shared_backward_host(H, A=None) -> BackwardFactor:
@@ -1028,6 +1079,16 @@ def factor_shared_backward_host(H, A=None) -> BackwardFactor:
 
 def solve_factored_backward_host(F: BackwardFactor, sol: Solution, gx, *, need=NEED_ALL):
     """numpy in / numpy out (qpb_solve_factored_backward_host): ``solve_factored_backward`` with host arrays."""
+    return _solve_factored_backward_host(F, sol, gx, None, need)
+
+
+def solve_factored_backward_dual_host(F: BackwardFactor, sol: Solution, gx, glam, *, need=NEED_ALL):
+    """numpy in / numpy out (qpb_solve_factored_backward_dual_host): ``solve_factored_backward_dual`` with host
+    arrays."""
+    return _solve_factored_backward_host(F, sol, gx, glam, need)
+
+
+def _solve_factored_backward_host(F: BackwardFactor, sol: Solution, gx, glam, need):
     import numpy as np
     need = _need_set(need)
     n, m = int(F.n), int(F.m)
@@ -1042,6 +1103,9 @@ def solve_factored_backward_host(F: BackwardFactor, sol: Solution, gx, *, need=N
     if gx.shape != (B, n) or x.shape != (B, n) or fac.shape != (factor_backward_doubles(n, m),) \
             or (m and (lam.shape != (B, m) or act.shape != (B, (m + 31) // 32))):
         raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    glam = None if glam is None or not m else np.ascontiguousarray(glam, dtype=np.float64)
+    if glam is not None and glam.shape != (B, m):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
     st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
     gH = np.zeros((n, n)) if "H" in need else None
     gf = np.zeros((B, n)) if "f" in need else None
@@ -1051,9 +1115,14 @@ def solve_factored_backward_host(F: BackwardFactor, sol: Solution, gx, *, need=N
         return None, None, None, None
     d = Desc(n, m, B, 0, 0, 0.0)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
-    rc = _lib.qpb_solve_factored_backward_host(ctypes.byref(d), p(fac), p(x), p(lam), p(act), p(st), p(gx), p(gH),
-                                               p(gf), p(gA), p(gb))
-    _check(rc, "qpb_solve_factored_backward_host")
+    if glam is None:
+        rc = _lib.qpb_solve_factored_backward_host(ctypes.byref(d), p(fac), p(x), p(lam), p(act), p(st), p(gx), p(gH),
+                                                   p(gf), p(gA), p(gb))
+        _check(rc, "qpb_solve_factored_backward_host")
+    else:
+        rc = _lib.qpb_solve_factored_backward_dual_host(ctypes.byref(d), p(fac), p(x), p(lam), p(act), p(st), p(gx),
+                                                        p(glam), p(gH), p(gf), p(gA), p(gb))
+        _check(rc, "qpb_solve_factored_backward_dual_host")
     return gH, gf, gA, gb
 
 
@@ -1368,6 +1437,102 @@ def solve_box_shared_backward_host(H, sol: Solution, gx, *, need=BOX_NEED_ALL):
                                                  p(glb), p(gub))
     _check(rc, "qpb_solve_box_shared_backward_host")
     return gH, gf, glb, gub
+
+
+def solve_box_backward_dual(H, sol: Solution, gx, glam, *, need=BOX_NEED_ALL, stream=None):
+    """``solve_box_backward`` (H (B, n, n)) or ``solve_box_shared_backward`` (a
+    2-D H (n, n): gH is ONE matrix, the sum over the batch) for a loss that also
+    reads the multipliers (qpb_solve_box_backward_dual).  ``glam = dl/dlam`` is
+    (B, 2n) in ``solve_box``'s lam layout, the upper bounds' entries first; on
+    unit rows it is a prescribed dx on the fixed variables (qpb.h has the
+    contract).  ``glam`` of a bound that is not active, of the lower bound of a
+    variable whose both bits are set and of QPs whose status is not OK is
+    ignored, whatever it holds.  ``glam=None`` is the call without it, bit for
+    bit.  n <= 32."""
+    import torch
+    if not (H.is_cuda and gx.is_cuda):
+        raise ValueError("qpb.solve_box_backward_dual expects CUDA (HIP) tensors; "
+                         "use solve_box_backward_dual_host for numpy")
+    if glam is None:
+        return (solve_box_shared_backward if H.dim() == 2 else solve_box_backward)(H, sol, gx, need=need,
+                                                                                  stream=stream)
+    B, n = gx.shape
+    for t in (H, gx, glam):
+        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64 CUDA tensors")
+    shared = SHARED_H if H.dim() == 2 else 0
+    if tuple(H.shape) != ((n, n) if shared else (B, n, n)) or tuple(glam.shape) != (B, 2 * n):
+        raise ValueError("shape mismatch: H must be (n, n) or (B, n, n) and glam (B, 2n)")
+    need = _box_need_set(need)
+    if not sol.x.is_cuda or sol.x.dtype != torch.float64 or not sol.x.is_contiguous() or sol.x.shape != (B, n):
+        raise ValueError("sol.x must be a contiguous float64 CUDA tensor of shape (B, n)")
+    if (sol.active is None or not sol.active.is_cuda or not sol.active.is_contiguous()
+            or sol.active.shape != (B, (2 * n + 31) // 32) or sol.active.element_size() != 4):
+        raise ValueError("sol.active must be a contiguous (B, ceil(2n/32)) CUDA tensor of 32-bit words")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or sol.status.shape != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    dev = gx.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    gH = new(*H.shape) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    glb = new(B, n) if "lb" in need else None
+    gub = new(B, n) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_box_backward_dual(ctypes.byref(d), shared, _ptr(H), _ptr(sol.x), _ptr(sol.active),
+                                          _ptr(sol.status), _ptr(gx), _ptr(glam), _ptr(gH), _ptr(gf), _ptr(glb),
+                                          _ptr(gub), _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_backward_dual")
+    return gH, gf, glb, gub
+
+
+def solve_box_backward_dual_host(H, sol: Solution, gx, glam, *, need=BOX_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_box_backward_dual_host): ``solve_box_backward_dual`` with host arrays."""
+    import numpy as np
+    need = _box_need_set(need)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    x = np.ascontiguousarray(sol.x, dtype=np.float64)
+    B, n = gx.shape
+    act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    glam = None if glam is None else np.ascontiguousarray(glam, dtype=np.float64)
+    shared = SHARED_H if H.ndim == 2 else 0
+    if H.shape != ((n, n) if shared else (B, n, n)) or x.shape != (B, n) or act.shape != (B, (2 * n + 31) // 32) \
+            or (glam is not None and glam.shape != (B, 2 * n)):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros(H.shape) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    glb = np.zeros((B, n)) if "lb" in need else None
+    gub = np.zeros((B, n)) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_backward_dual_host(ctypes.byref(d), shared, p(H), p(x), p(act), p(st), p(gx), p(glam),
+                                               p(gH), p(gf), p(glb), p(gub))
+    _check(rc, "qpb_solve_box_backward_dual_host")
+    return gH, gf, glb, gub
+
+
+def solve_box_tangent(H, sol: Solution, df, dlb=None, dub=None, *, stream=None):
+    """The forward sensitivity of a box solve: the tangent ``(dx, dlam)`` of
+    (x*, lam*) along a change ``df`` of f and ``dlb``, ``dub`` (B, n) of the
+    bounds, at fixed active set; ``dlam`` is (B, 2n) in ``solve_box``'s lam
+    layout.  ONE call of ``solve_box_backward_dual`` with ``gx = df``,
+    ``glam[:, :n] = -dub``, ``glam[:, n:] = +dlb`` and ``need = ("f", "lb",
+    "ub")``: ``dx = gf``, ``dlam = [-gub, +glb]``.  A fixed variable moves with
+    its bound and a free one follows through H; ``dlam`` is 0 on a bound that
+    is not active.  H (B, n, n), or (n, n) for one H.  With ``dlb`` and ``dub``
+    None the bounds do not move and the call runs the box backward's kernels."""
+    import contextlib
+
+    import torch
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        glam = None
+        if dlb is not None or dub is not None:
+            z = torch.zeros_like(df)
+            glam = torch.cat((z if dub is None else -dub, z if dlb is None else dlb), dim=1).contiguous()
+        _, dx, glb, gub = solve_box_backward_dual(H, sol, df, glam, need=("f", "lb", "ub"), stream=stream)
+        return dx, torch.cat((-gub, glb), dim=1)
 
 
 def active_mask_to_bool(active, m: int):

@@ -40,7 +40,15 @@ factored one in the same way.
 return ``(x, lam, status)`` with x AND lam differentiable: the backward is
 ``qpb.solve_backward_dual`` (qpb_solve_backward_dual, the same KKT system with
 the cotangent on lam as its lower right-hand side).  A loss that does not read
-lam takes the backward of ``solve`` / ``solve_range``, bit for bit.
+lam takes the backward of ``solve`` / ``solve_range``, bit for bit.  With
+``prefactor=True`` (a 2-D H and a 2-D A) both passes run on factor buffers as
+in ``solve`` / ``solve_range``, the backward by
+``qpb.solve_factored_backward_dual``, with the default's gradients bit for bit.
+
+``solve_box_dual(H, f, lb, ub)`` is the same for box QPs: ``(x, lam, status)``
+with lam (B, 2n) in ``qpb.solve_box``'s layout, the backward
+``qpb.solve_box_backward_dual``; H 2-D or 3-D and ``prefactor`` as in
+``solve_box``.
 """
 from __future__ import annotations
 
@@ -178,9 +186,11 @@ def _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted):
     sol = qpb.Solution(x, lam, active, status, None)
     gx = torch.zeros_like(x) if gx is None else gx.contiguous()
     if glam is None:
-        backward = qpb.solve_shared_backward if ctx.shared else qpb.solve_backward
-        return backward(H, A, sol, gx, need=wanted)
+        return _backward(ctx, H, A, sol, gx, wanted)
     # on torch's current stream; above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
+    if ctx.prefactor:
+        return qpb.solve_factored_backward_dual(qpb.factor_shared_backward(H, A), sol, gx, glam.contiguous(),
+                                                need=wanted)
     return qpb.solve_backward_dual(H, A, sol, gx, glam.contiguous(), need=wanted)
 
 
@@ -188,10 +198,13 @@ class DualQPFunction(torch.autograd.Function):
     """(x*, lam*)(H, f, A, b) of min 1/2 x'Hx + f'x s.t. A[:meq] x = b[:meq], A[meq:] x <= b[meq:]."""
 
     @staticmethod
-    def forward(ctx, H, f, A, b, meq, max_iter, feas_tol):
+    def forward(ctx, H, f, A, b, meq, max_iter, feas_tol, prefactor=False):
         H, f, A, b = H.contiguous(), f.contiguous(), A.contiguous(), b.contiguous()
         ctx.shared = H.dim() == 2 or A.dim() == 2
-        if ctx.shared:
+        ctx.prefactor = prefactor
+        if prefactor:
+            sol = qpb.solve_factored(qpb.factor_shared(H, A), f, b, meq, max_iter=max_iter, feas_tol=feas_tol)
+        elif ctx.shared:
             sol = qpb.solve_shared(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
         else:
             sol = qpb.solve_eq(H, f, A, b, meq, max_iter=max_iter, feas_tol=feas_tol)
@@ -205,22 +218,27 @@ class DualQPFunction(torch.autograd.Function):
         H, A, x, lam, active, status = ctx.saved_tensors
         wanted = [k for k, w in zip("HfAb", ctx.needs_input_grad[:4]) if w]
         if not wanted or (gx is None and glam is None):
-            return (None,) * 7
+            return (None,) * 8
         gH, gf, gA, gb = _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted)
-        return gH, gf, gA, gb, None, None, None
+        return gH, gf, gA, gb, None, None, None, None
 
 
 class RangeDualQPFunction(torch.autograd.Function):
     """(x*, lam*)(H, f, A, bl, bu) of ``RangeQPFunction``'s problem, lam signed."""
 
     @staticmethod
-    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol):
+    def forward(ctx, H, f, A, bl, bu, meq, max_iter, feas_tol, prefactor=False):
         H, f, A = H.contiguous(), f.contiguous(), A.contiguous()
         bl = None if bl is None else bl.contiguous()
         bu = None if bu is None else bu.contiguous()
         # above n = 32 or m = 64 this raises QPBError(ERR_UNSUPPORTED)
-        sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
+        if prefactor:
+            sol = qpb.solve_range_factored(qpb.factor_shared(H, A), f, bl, bu, meq, max_iter=max_iter,
+                                           feas_tol=feas_tol)
+        else:
+            sol = qpb.solve_range(H, f, A, bl, bu, meq, max_iter=max_iter, feas_tol=feas_tol)
         ctx.shared = H.dim() == 2 or A.dim() == 2
+        ctx.prefactor = prefactor
         ctx.has = (True, True, True, bl is not None, bu is not None)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(H, A, sol.x, sol.lam, sol.active, sol.lower, sol.status)
@@ -233,7 +251,7 @@ class RangeDualQPFunction(torch.autograd.Function):
         want = [w and has for w, has in zip(ctx.needs_input_grad[:5], ctx.has)]
         wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if want[3] or want[4] else [])
         if not wanted or (gx is None and glam is None):
-            return (None,) * 8
+            return (None,) * 9
         gH, gf, gA, gb = _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted)
         gbl = gbu = None
         if gb is not None:
@@ -246,10 +264,64 @@ class RangeDualQPFunction(torch.autograd.Function):
                 gbl = torch.where(low, gb, zero)
             if want[4]:
                 gbu = torch.where(low, zero, gb)
-        return gH, gf, gA, gbl, gbu, None, None, None
+        return gH, gf, gA, gbl, gbu, None, None, None, None
 
 
-def solve_dual(H, f, A, b, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+class BoxDualQPFunction(torch.autograd.Function):
+    """(x*, lam*)(H, f, lb, ub) of ``BoxQPFunction``'s problem, lam (B, 2n): the upper bounds' entries, then the
+    lower bounds'."""
+
+    @staticmethod
+    def forward(ctx, H, f, lb, ub, max_iter, feas_tol, prefactor):
+        H, f = H.contiguous(), f.contiguous()
+        lb = None if lb is None else lb.contiguous()
+        ub = None if ub is None else ub.contiguous()
+        ctx.shared = H.dim() == 2  # one H for the batch
+        if prefactor:
+            # above n = 32 this raises QPBError(ERR_UNSUPPORTED)
+            sol = qpb.solve_box_factored(qpb.factor_box(H), f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        else:
+            forward = qpb.solve_box_shared if ctx.shared else qpb.solve_box
+            sol = forward(H, f, lb, ub, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.has = (True, True, lb is not None, ub is not None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(H, sol.x, sol.active, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.lam, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, glam, _gstatus):
+        H, x, active, status = ctx.saved_tensors
+        names = ("H", "f", "lb", "ub")
+        wanted = [k for k, w, has in zip(names, ctx.needs_input_grad[:4], ctx.has) if w and has]
+        if not wanted or (gx is None and glam is None):
+            return (None,) * 7
+        sol = qpb.Solution(x, None, active, status, None)
+        gx = torch.zeros_like(x) if gx is None else gx.contiguous()
+        # on torch's current stream; above n = 32 this raises QPBError(ERR_UNSUPPORTED).  An unused lam
+        # arrives as None and takes solve_box's backward.
+        gH, gf, glb, gub = qpb.solve_box_backward_dual(H, sol, gx, None if glam is None else glam.contiguous(),
+                                                       need=wanted)
+        return gH, gf, glb, gub, None, None, None
+
+
+def solve_box_dual(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):
+    """``solve_box`` that also returns the multipliers, differentiably: returns
+    ``(x, lam, status)`` with ``lam`` (B, 2n) in ``qpb.solve_box``'s layout, the
+    upper bounds' entries first; ``x`` and ``lam`` both carry gradients to
+    whichever of H, f, lb and ub require them.  The backward is
+    ``qpb.solve_box_backward_dual`` on the two cotangents at fixed active set; a
+    loss that does not read ``lam`` gets ``solve_box``'s gradients bit for bit,
+    and one that does not read ``x`` has gx = 0.  H 2-D (one matrix, its
+    gradient the sum over the batch) or 3-D, and ``prefactor``, as in
+    ``solve_box``.  The backward needs n <= 32."""
+    if prefactor:
+        if H.dim() != 2:
+            raise ValueError("prefactor=True needs a 2-D H (n, n): one matrix for the batch")
+    return BoxDualQPFunction.apply(H, f, lb, ub, int(max_iter), float(feas_tol), bool(prefactor))
+
+
+def solve_dual(H, f, A, b, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):
     """``solve`` that also returns the multipliers, differentiably: returns
     ``(x, lam, status)``; ``x`` and ``lam`` (B, m, H x + f + A' lam = 0) both carry
     gradients to whichever of H, f, A and b require them -- shadow prices,
@@ -260,13 +332,21 @@ def solve_dual(H, f, A, b, meq: int = 0, *, max_iter: int = 0, feas_tol: float =
     (m, n) is shared by the batch, its gradient the sum over the batch.  QPs whose
     status is not OK contribute zero gradients.  n <= 32 and m <= 64 in the
     backward (``QPBError(ERR_UNSUPPORTED)`` above).  A is required (without rows
-    there is no lam: use ``solve``); no ``prefactor`` yet."""
+    there is no lam: use ``solve``).  ``prefactor=True`` needs a 2-D H and a 2-D
+    A, else ValueError: the forward is ``solve``'s prefactored one, and the
+    backward factors H and A once (``qpb.factor_shared_backward``) and runs
+    ``qpb.solve_factored_backward_dual``, with the default's gradients bit for
+    bit.  The default is today's call, bit for bit."""
     if A is None or b is None:
         raise ValueError("qpb.diff.solve_dual needs A and b: without rows there are no multipliers (use solve)")
-    return DualQPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol))
+    if prefactor:
+        if H.dim() != 2 or A.dim() != 2:
+            raise ValueError("prefactor=True needs a 2-D H (n, n) and a 2-D A (m, n): one matrix for the batch")
+    return DualQPFunction.apply(H, f, A, b, int(meq), int(max_iter), float(feas_tol), bool(prefactor))
 
 
-def solve_range_dual(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+def solve_range_dual(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                     prefactor: bool = False):
     """``solve_range`` that also returns the signed multipliers, differentiably:
     returns ``(x, lam, status)`` with ``lam`` in ``qpb.solve_range``'s convention
     (H x + f + A' lam = 0: >= 0 on a row active at bu, <= 0 at bl).  The backward
@@ -274,8 +354,13 @@ def solve_range_dual(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_t
     ``bl`` where the ``lower`` bit is set and to ``bu`` everywhere else, exactly
     as in ``solve_range``.  A bound passed as None gets no gradient.  A loss that
     does not read ``lam`` gets ``solve_range``'s gradients bit for bit.  n <= 32
-    and m <= 64; no ``prefactor`` yet."""
-    return RangeDualQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol))
+    and m <= 64.  ``prefactor=True`` (a 2-D H and a 2-D A, else ValueError) is
+    ``solve_range``'s prefactored forward and ``qpb.solve_factored_backward_dual``
+    in the backward, with the default's gradients bit for bit."""
+    if prefactor:
+        if H.dim() != 2 or A.dim() != 2:
+            raise ValueError("prefactor=True needs a 2-D H (n, n) and a 2-D A (m, n): one matrix for the batch")
+    return RangeDualQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol), bool(prefactor))
 
 
 def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,

@@ -22,6 +22,7 @@
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
  *   ... differentiated on the H and A factored once           qpb_factor_shared_backward, qpb_solve_factored_backward
+ *   ... that, and the box backward, for a loss that reads lam  qpb_solve_factored_backward_dual, qpb_solve_box_backward_dual
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -510,9 +511,9 @@ int qpb_solve_shared_backward_host(const qpb_desc *desc, int32_t shared,
  * `shared` outside QPB_SHARED_H | QPB_SHARED_A QPB_ERR_INVALID_ARG; n > 32 or
  * m > 64 QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the pointers are
  * looked at; missing pointers QPB_ERR_INVALID_ARG; a missing device last.
- * Follow-ups: the factored form (glam on a qpb_factor_shared_backward buffer);
- * a glam for qpb_solve_box_backward, which there is a prescribed dx on the
- * fixed variables; the n <= 128 Gram class.
+ * The factored form (glam on a qpb_factor_shared_backward buffer) is
+ * qpb_solve_factored_backward_dual and the box form qpb_solve_box_backward_dual,
+ * both below.  Follow-up: the n <= 128 Gram class.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_backward_dual(const qpb_desc *desc, int32_t shared,
 			    const double *H, const double *A, const double *x,
@@ -755,6 +756,47 @@ int qpb_solve_factored_backward_host(const qpb_desc *desc, const double *bfac,
 				     double *gH, double *gf, double *gA,
 				     double *gb);
 
+/* qpb_solve_backward_dual(shared = QPB_SHARED_H | QPB_SHARED_A) on a buffer of
+ * qpb_factor_shared_backward, without H and A: qpb_solve_factored_backward for a
+ * loss l(x, lam) that also reads the multipliers, and the f / b tangent on the
+ * path that factors once (gx = df, glam = -db: gf is dx*, -gb is dlam*).
+ *   glam            B x m, in lam's layout and sign convention, as
+ *                   qpb_solve_backward_dual's.
+ *   outputs         every non-NULL output equals BIT FOR BIT what
+ *                   qpb_solve_backward_dual writes with both operands shared,
+ *                   for the same x, lam, active, status, gx and glam on the H
+ *                   and A the buffer was made from.
+ *   glam == NULL,   the call is qpb_solve_factored_backward: the same launches,
+ *   or m == 0       the same outputs bit for bit.
+ *   glam outside W  ignored, whatever it holds, NaN included; so is the glam of
+ *                   a row the orthogonalisation skips and of a QP whose status
+ *                   is not QPB_OK (zeros everywhere, exactly 0 to the sums).
+ * Everything else is qpb_solve_factored_backward's: a buffer whose H was not
+ * SPD gives zeros everywhere, the workspace, the reproducibility of the sums,
+ * the buffer only read, bfac 16-byte aligned.  The layout of the buffer does
+ * not change: R and Q are per QP and come from the orthogonalisation.
+ * Pass 1 is the DU forms of the factored forms of qpb_kkt_bwd.hip -- the
+ * factored load and u recursion, then qpb_solve_backward_dual's four steps
+ * after the orthogonalisation, the same code -- and pass 2 is unchanged.
+ * Errors, in order, are qpb_solve_factored_backward's; glam is never required.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_factored_backward_dual(const qpb_desc *desc, const double *bfac,
+				     const double *x, const double *lam,
+				     const uint32_t *active,
+				     const int32_t *status, const double *gx,
+				     const double *glam, double *gH, double *gf,
+				     double *gA, double *gb, void *stream);
+
+/* Same with host pointers (bfac included: the call uploads it). */
+int qpb_solve_factored_backward_dual_host(const qpb_desc *desc,
+					  const double *bfac, const double *x,
+					  const double *lam,
+					  const uint32_t *active,
+					  const int32_t *status,
+					  const double *gx, const double *glam,
+					  double *gH, double *gf, double *gA,
+					  double *gb);
+
 /* Box-constrained batched solve, lb <= x <= ub: the constraint class of the
  * reference's admm() (qp_solvers.c:146-319, bounds config.h:29-30), solved
  * exactly with A = [I; -I], b = [ub; -lb] kept implicit (qpb_gi_box.hip for
@@ -909,6 +951,67 @@ int qpb_solve_box_shared_backward_host(const qpb_desc *desc, const double *H,
 				       const int32_t *status, const double *gx,
 				       double *gH, double *gf, double *glb,
 				       double *gub);
+
+/* qpb_solve_box_backward and qpb_solve_box_shared_backward for a loss l(x, lam)
+ * that also reads the multipliers: the KKT system of qpb_solve_backward_dual on
+ * A = [I; -I] at FIXED active set, with the unit rows eliminated.  There glam
+ * is a prescribed dx on the fixed variables.  S: the fixed variables, F: the
+ * free ones,
+ *
+ *     d_j = -glam[j]        the upper bit of j is set
+ *     d_j = +glam[n + j]    only the lower bit of j is set
+ *     d_j = 0               j is free
+ *     dx_S = d_S (exactly those bits)      H_FF dx_F = -gx_F - H_FS d_S
+ *     r = gx + H dx
+ *
+ * and the box backward's output formulas, unchanged: gf = dx,
+ * gH = 1/2 (dx x^T + x dx^T) (symmetric bit for bit), gub_j = r_j on an active
+ * upper bound, glb_j = r_j on a lower bound that is active without the upper.
+ * The same call is the tangent of (x*, lam*) along (df, dlb, dub): with gx = df,
+ * glam[:n] = -dub and glam[n:] = +dlb, gf is dx*, -gub is dlam* of the upper
+ * bounds and +glb of the lower ones.
+ *   glam            B x 2n in qpb_solve_box's lam layout: the upper bounds'
+ *                   entries, then the lower bounds'.
+ *   shared          0: H is B x n x n and gH per QP, as qpb_solve_box_backward.
+ *                   QPB_SHARED_H: H is n x n and gH ONE n x n sum, exactly as
+ *                   qpb_solve_box_shared_backward -- pass 1 without the gH
+ *                   stores, pass 2 with m = 0, the same workspace, the same
+ *                   reproducible bits; gf, glb and gub are the unshared call's
+ *                   bit for bit.
+ *   both bits set   the upper bound counts; the lower row is the dependent one:
+ *                   its glam is ignored and glb_j = 0 (qpb_solve_box_backward's
+ *                   rule).
+ *   ignored         the glam of a bit that is clear, of bits >= 2n and of a QP
+ *                   whose status is not QPB_OK, whatever it holds, NaN included.
+ *                   Such a QP gets zeros and contributes exactly 0 to the sum.
+ *   glam == NULL    the call is qpb_solve_box_backward (shared == 0) or
+ *                   qpb_solve_box_shared_backward: the same launches, the same
+ *                   outputs bit for bit.
+ * The kernels are the DU forms of qpb_kkt_bwd_box.hip, plain and SH.  The masked
+ * Cholesky is untouched; per QP the new work is d from glam and the mask, one
+ * product of the untouched rows of H (held for r) with d, and d in place of 0
+ * on the fixed variables.
+ * Errors, in order: the descriptor as qpb_solve_box (m != 2n
+ * QPB_ERR_INVALID_ARG); flags != 0 and a bit of `shared` other than
+ * QPB_SHARED_H QPB_ERR_INVALID_ARG; n > 32 QPB_ERR_UNSUPPORTED; batch == 0
+ * returns 0 before the pointers are looked at; missing pointers
+ * QPB_ERR_INVALID_ARG (H, x, active and gx; at least one output); a missing
+ * device last.  glam is never required.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_box_backward_dual(const qpb_desc *desc, int32_t shared,
+				const double *H, const double *x,
+				const uint32_t *active, const int32_t *status,
+				const double *gx, const double *glam,
+				double *gH, double *gf, double *glb,
+				double *gub, void *stream);
+
+/* Same with host pointers (with QPB_SHARED_H, H and gH are one matrix each). */
+int qpb_solve_box_backward_dual_host(const qpb_desc *desc, int32_t shared,
+				     const double *H, const double *x,
+				     const uint32_t *active,
+				     const int32_t *status, const double *gx,
+				     const double *glam, double *gH, double *gf,
+				     double *glb, double *gub);
 
 /* ONE H for a batch of box QPs, factored ONCE.  With H shared, the set-up of
  * every QP -- H = L L^T and the rows of L^-T, which are the rows of
