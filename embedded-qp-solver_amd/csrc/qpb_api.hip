@@ -1735,6 +1735,187 @@ extern "C" int qpb_generate(const qpb_gen_desc *d, double *H, double *f, double 
   return 0;
 }
 
+// ---- T right-hand sides per QP in one launch ----------------------------------
+static_assert(QPB_MAX_RHS == qpb::kMaxRhs && (QPB_SHARED_RHS & (QPB_SHARED_H | QPB_SHARED_A)) == 0);
+
+// qpb_solve_factored_backward_multi's argument rules after check_desc, up to batch == 0
+static int check_factored_bwd_multi(const qpb_desc *d, int32_t nrhs, int32_t shared) {
+  static const char what[] = "qpb_solve_factored_backward_multi";
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "%s: flags must be 0 (got %d)", what, d->flags);
+  if (shared & ~QPB_SHARED_RHS)
+    return fail(QPB_ERR_INVALID_ARG, "%s: shared must be 0 or QPB_SHARED_RHS (got %d)", what, shared);
+  if (nrhs < 1 || nrhs > QPB_MAX_RHS)
+    return fail(QPB_ERR_INVALID_ARG, "%s: nrhs must be 1..%d (got %d)", what, QPB_MAX_RHS, nrhs);
+  if (qpb::route_factored_bwd_multi(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "%s: n=%d m=%d outside the factored backward kernels (n<=%d, m<=%d)", what, d->n,
+                d->m, qpb::kBwdMultiMaxN, qpb::kBwdMultiMaxM);
+  return 0;
+}
+// ... and the pointers (device or host)
+static int check_factored_bwd_multi_arrays(const qpb_desc *d, const double *bfac, const uint32_t *active,
+                                           const double *gx, const double *gf, const double *gb) {
+  static const char what[] = "qpb_solve_factored_backward_multi";
+  if (!bfac || !gx) return fail(QPB_ERR_INVALID_ARG, "%s: bfac and gx are required", what);
+  if (d->m > 0 && !active) return fail(QPB_ERR_INVALID_ARG, "%s: active is required when m > 0", what);
+  if (!gf && !(d->m > 0 && gb)) return fail(QPB_ERR_INVALID_ARG, "%s: at least one of gf and gb is required", what);
+  return 0;
+}
+
+extern "C" int qpb_solve_factored_backward_multi(const qpb_desc *d, const double *bfac, const uint32_t *active,
+                                                 const int32_t *status, int32_t nrhs, int32_t shared,
+                                                 const double *gx, const double *glam, double *gf, double *gb,
+                                                 void *stream) {
+  static const char what[] = "qpb_solve_factored_backward_multi";
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_factored_bwd_multi(d, nrhs, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_factored_bwd_multi_arrays(d, bfac, active, gx, gf, gb);
+  if (rc) return rc;
+  if ((uintptr_t)bfac & 15) return fail(QPB_ERR_INVALID_ARG, "%s: bfac must be 16-byte aligned", what);
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_factored_bwd_multi(d->n, d->m);
+  const long long n = d->n, m = d->m, T = nrhs;
+  if (m == 0) glam = nullptr, gb = nullptr;  // ignored
+  // the right-hand sides' QP stride in directions: 0 for the one shared set, in the kernels and in the chunk walk
+  const long long rs = (shared & QPB_SHARED_RHS) ? 0 : T;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Fc, const uint32_t *ac, const int32_t *sc, const double *gxc,
+          const double *glc, double *gfc, double *gbc) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e =
+            qpb_launch_kkt_bwd_factored_multi(&c, Fc, ac, sc, nrhs, rs, gxc, glc, gfc, gbc, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+      },
+      qpb::required(bfac, 0), qpb::optional(active, (m + 31) / 32), qpb::optional(status, 1),
+      qpb::required(gx, rs * n), qpb::optional(glam, rs * m), qpb::optional(gf, T * n), qpb::optional(gb, T * m));
+}
+
+extern "C" int qpb_solve_factored_backward_multi_host(const qpb_desc *d, const double *bfac, const uint32_t *active,
+                                                      const int32_t *status, int32_t nrhs, int32_t shared,
+                                                      const double *gx, const double *glam, double *gf, double *gb) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_factored_bwd_multi(d, nrhs, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_factored_bwd_multi_arrays(d, bfac, active, gx, gf, gb);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, m = d->m, w = (m + 31) / 32, T = (size_t)nrhs;
+  const size_t BR = (shared & QPB_SHARED_RHS) ? 1 : B;
+  DevBuf dF, da, ds, dg, dgl, of, ob;
+  HIPCHK(up(dF, bfac, (size_t)qpb::bfct::layout(d->n, d->m).size * 8), "bfac");
+  HIPCHK(up(da, m ? active : nullptr, B * w * 4), "active");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, BR * T * n * 8), "gx");
+  HIPCHK(up(dgl, m ? glam : nullptr, BR * T * m * 8), "glam");
+  HIPCHK(alloc(of, gf, B * T * n * 8), "gf");
+  HIPCHK(alloc(ob, m ? gb : nullptr, B * T * m * 8), "gb");
+  rc = qpb_solve_factored_backward_multi(d, (double *)dF.p, (uint32_t *)da.p, (int32_t *)ds.p, nrhs, shared,
+                                         (double *)dg.p, (double *)dgl.p, (double *)of.p, (double *)ob.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_factored_backward_multi_host kernel");
+  HIPCHK(down(gf, of, B * T * n * 8), "gf D2H");
+  HIPCHK(down(m ? gb : nullptr, ob, B * T * m * 8), "gb D2H");
+  return 0;
+}
+
+// qpb_solve_box_backward_multi's argument rules after check_desc, up to batch == 0
+static int check_bwd_box_multi(const qpb_desc *d, int32_t nrhs, int32_t shared) {
+  static const char what[] = "qpb_solve_box_backward_multi";
+  if (d->m != 2 * d->n) return fail(QPB_ERR_INVALID_ARG, "%s: m must be 2n (got n=%d m=%d)", what, d->n, d->m);
+  if (d->flags != 0) return fail(QPB_ERR_INVALID_ARG, "%s: flags must be 0 (got %d)", what, d->flags);
+  if (shared & ~(QPB_SHARED_H | QPB_SHARED_RHS))
+    return fail(QPB_ERR_INVALID_ARG, "%s: shared must be a combination of QPB_SHARED_H and QPB_SHARED_RHS (got %d)",
+                what, shared);
+  if (nrhs < 1 || nrhs > QPB_MAX_RHS)
+    return fail(QPB_ERR_INVALID_ARG, "%s: nrhs must be 1..%d (got %d)", what, QPB_MAX_RHS, nrhs);
+  if (qpb::route_bwd_box_multi(d->n).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED, "%s: n=%d outside the backward box kernels (n<=%d)", what, d->n,
+                qpb::kBwdBoxMultiMaxN);
+  return 0;
+}
+// ... and the pointers (device or host)
+static int check_bwd_box_multi_arrays(const double *H, const uint32_t *active, const double *gx, const double *gf,
+                                      const double *glb, const double *gub) {
+  static const char what[] = "qpb_solve_box_backward_multi";
+  if (!H || !active || !gx) return fail(QPB_ERR_INVALID_ARG, "%s: H, active and gx are required", what);
+  if (!gf && !glb && !gub) return fail(QPB_ERR_INVALID_ARG, "%s: at least one of gf, glb and gub is required", what);
+  return 0;
+}
+
+extern "C" int qpb_solve_box_backward_multi(const qpb_desc *d, int32_t shared, const double *H,
+                                            const uint32_t *active, const int32_t *status, int32_t nrhs,
+                                            const double *gx, const double *glam, double *gf, double *glb,
+                                            double *gub, void *stream) {
+  static const char what[] = "qpb_solve_box_backward_multi";
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box_multi(d, nrhs, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_multi_arrays(H, active, gx, gf, glb, gub);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const qpb::Route r = qpb::route_bwd_box_multi(d->n);
+  const long long n = d->n, m = d->m, T = nrhs;
+  // a shared operand's QP stride is 0, in the kernels and in the chunk walk
+  const long long sH = (shared & QPB_SHARED_H) ? 0 : n * n, rs = (shared & QPB_SHARED_RHS) ? 0 : T;
+  return qpb::for_each_chunk(
+      d->batch, r.step,
+      [&](long long count, const double *Hc, const uint32_t *ac, const int32_t *sc, const double *gxc,
+          const double *gmc, double *gfc, double *glc, double *guc) {
+        qpb_desc c = *d;
+        c.batch = count;
+        const hipError_t e =
+            qpb_launch_kkt_bwd_box_multi(&c, sH, Hc, ac, sc, nrhs, rs, gxc, gmc, gfc, glc, guc, (hipStream_t)stream);
+        return e == hipSuccess ? 0 : fail(QPB_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+      },
+      qpb::required(H, sH), qpb::required(active, (m + 31) / 32), qpb::optional(status, 1), qpb::required(gx, rs * n),
+      qpb::optional(glam, rs * m), qpb::optional(gf, T * n), qpb::optional(glb, T * n), qpb::optional(gub, T * n));
+}
+
+extern "C" int qpb_solve_box_backward_multi_host(const qpb_desc *d, int32_t shared, const double *H,
+                                                 const uint32_t *active, const int32_t *status, int32_t nrhs,
+                                                 const double *gx, const double *glam, double *gf, double *glb,
+                                                 double *gub) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_bwd_box_multi(d, nrhs, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_bwd_box_multi_arrays(H, active, gx, gf, glb, gub);  // host pointers: the same rules
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  const size_t B = (size_t)d->batch, n = d->n, w = (2 * n + 31) / 32, T = (size_t)nrhs;
+  const size_t BH = (shared & QPB_SHARED_H) ? 1 : B, BR = (shared & QPB_SHARED_RHS) ? 1 : B;
+  DevBuf dH, da, ds, dg, dgl, of, ol, ou;
+  HIPCHK(up(dH, H, BH * n * n * 8), "H");
+  HIPCHK(up(da, active, B * w * 4), "active");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, BR * T * n * 8), "gx");
+  HIPCHK(up(dgl, glam, BR * T * 2 * n * 8), "glam");
+  HIPCHK(alloc(of, gf, B * T * n * 8), "gf");
+  HIPCHK(alloc(ol, glb, B * T * n * 8), "glb");
+  HIPCHK(alloc(ou, gub, B * T * n * 8), "gub");
+  rc = qpb_solve_box_backward_multi(d, shared, (double *)dH.p, (uint32_t *)da.p, (int32_t *)ds.p, nrhs, (double *)dg.p,
+                                    (double *)dgl.p, (double *)of.p, (double *)ol.p, (double *)ou.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_box_backward_multi_host kernel");
+  HIPCHK(down(gf, of, B * T * n * 8), "gf D2H");
+  HIPCHK(down(glb, ol, B * T * n * 8), "glb D2H");
+  HIPCHK(down(gub, ou, B * T * n * 8), "gub D2H");
+  return 0;
+}
+
 extern "C" int qpb_device_count(void) {
   int c = 0;
   if (hipGetDeviceCount(&c) != hipSuccess) return 0;

@@ -107,6 +107,32 @@ using Form = std::integral_constant<int, FM>;
 // forms have no such argument and none of this code.  On a buffer (FM == 2,
 // qpb_solve_factored_backward_dual) the four steps are the same code behind the
 // factored load: R and Q are per QP, from the orthogonalisation, either way.
+// MU (qpb_solve_factored_backward_multi, both kernels, on a buffer only: FM ==
+// 2, with and without glam): T right-hand sides per QP.  The pack's last
+// argument, a Multi, which only this form has, carries T and the QP stride of
+// the right-hand sides in directions (T, or 0 for one set that the whole batch
+// reads).  Direction t of QP k reads gx + (k stride + t) n and glam +
+// (k stride + t) m and writes gf + (k T + t) n and gb + (k T + t) m.  The
+// factored load and the orthogonalisation run once -- neither reads gx -- and
+// L, 1 / L_kk, Q, R and the rows' positions stay where they are; a loop over t
+// takes u from the buffer's multipliers and repeats the rest of the
+// single-direction form operation for operation, so every direction's bits are
+// that form's.  x, lam, gH and gA are not arguments of the call: NULL, never read.
+struct Multi {
+  int T;
+  long long stride;
+};
+template <class... GL>
+inline constexpr bool tail_is_multi = (std::is_same_v<GL, Multi> || ...);
+template <class... GL>
+inline constexpr bool tail_ok = std::is_same_v<void(GL...), void()> || std::is_same_v<void(GL...), void(const double *)> ||
+                                std::is_same_v<void(GL...), void(Multi)> ||
+                                std::is_same_v<void(GL...), void(const double *, Multi)>;
+__device__ __forceinline__ const double *tail_glam(const double *p) { return p; }
+__device__ __forceinline__ const double *tail_glam(const double *p, Multi) { return p; }
+__device__ __forceinline__ Multi tail_multi(Multi mu) { return mu; }
+__device__ __forceinline__ Multi tail_multi(const double *, Multi mu) { return mu; }
+
 template <int MR, bool N16, bool SH = false, class... FMP, class... GL>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     const double *__restrict__ Hg, const double *__restrict__ Ag, const double *__restrict__ xg,
@@ -115,9 +141,10 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     double *__restrict__ gbg, int n, int m, long long batch, GL... glamg) {
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
-  constexpr bool DU = sizeof...(GL) == 1;
-  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM == 1),
-                "glam is one array, beside H and A or a buffer of them");
+  constexpr bool MU = tail_is_multi<GL...>;
+  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) == 1;
+  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2),
+                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only");
   __shared__ double lds[QPB * SLOT];
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -145,9 +172,10 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   // a QP that is not QPB_OK takes no trips and stores zeros
   uint32_t W = (m > 0 && ok) ? form_mask<FM>(actg, g) : 0u;
   if (m < 32) W &= (1u << m) - 1u;
-  const double gv = form_gx<FM>(gxg, g * n + lc);
+  double gv = 0.0;  // (MU: per direction, below)
+  if constexpr (!MU) gv = form_gx<FM>(gxg, g * n + lc);
   [[maybe_unused]] double gl[MR];  // DU: glam of the lane's rows, 0 outside W (whatever it holds there)
-  if constexpr (DU) {
+  if constexpr (DU && !MU) {
     const double *__restrict__ glq = (glamg, ...) + g * (long long)m;  // (the form has m > 0)
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
@@ -172,6 +200,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
       if ((t * NL + l) * 2 < L_SIZE) *reinterpret_cast<double2 *>(&Lp[(t * NL + l) * 2]) = v;
     }
     invLd = fac[y.ik + l];
+    if constexpr (!MU) {  // (MU takes every direction's u behind the orthogonalisation; the block keeps its indentation)
     double nc[NL];
 #pragma unroll
     for (int t = 0; t < NL / 2; ++t) {
@@ -192,6 +221,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
     // (D after u: the multipliers are dead by then, and nothing may hoist the
     // loads above it -- the 32 registers of nc beside the 64 of D spill)
     __builtin_amdgcn_sched_barrier(0);
+    }  // !MU
 #pragma unroll
     for (int r = 0; r < MR; ++r)
 #pragma unroll
@@ -401,6 +431,118 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
 
   // ---- z = -(u - Q Q^T u), R dlam = -Q^T u
   const int qmax = wave_max4(cnt);
+  if constexpr (MU) {
+    // ---- T directions on the one load and orthogonalisation.  Per direction:
+    // the multipliers again from the buffer (hot in cache; D's registers are
+    // dead by now), the u recursion of the factored load, and the statements
+    // below from the two projection passes to the stores of gf and gb.
+    const Multi mu = tail_multi(glamg...);
+    constexpr bfct::Layout fy = bfct::layout(NL, NL * MR);
+    const double *__restrict__ fac = Hg;
+    const bool lives = ragged_qp(blockIdx.x, slot, batch).live;
+    const double *__restrict__ gq = gxg + g * mu.stride * n + lc;
+    [[maybe_unused]] const double *__restrict__ glq = nullptr;
+    if constexpr (DU) glq = tail_glam(glamg...) + g * mu.stride * m;  // (the form has m > 0)
+    for (int t = 0; t < mu.T; ++t) {
+      const double gt = gq[(long long)t * n];
+      [[maybe_unused]] double glt[MR];  // glam of the lane's rows, 0 outside W (whatever it holds there)
+      if constexpr (DU) {
+#pragma unroll
+        for (int r = 0; r < MR; ++r) {
+          const int row = l + NL * r;
+          const double v = glq[(long long)t * m + (row < m ? row : 0)];
+          glt[r] = ((W >> row) & 1u) ? v : 0.0;
+        }
+      }
+      double yt = var ? gt : 0.0, ut = 0.0;
+      {
+        double nc[NL];
+#pragma unroll
+        for (int h = 0; h < NL / 2; ++h) {
+          const double2 v = *reinterpret_cast<const double2 *>(&fac[fy.nc + (h * NL + l) * 2]);
+          nc[2 * h] = v.x;
+          nc[2 * h + 1] = v.y;
+        }
+        unroll<NL>([&](auto K) {
+          constexpr int k = K;
+          ut = l == k ? yt * invLd : ut;
+          pin(ut);
+          fmac_bc_nop<k>(yt, yt, nc[k]);
+        });
+      }
+      double z = ut, cu = 0.0;
+      project(z, cu, qmax);
+      project(z, cu, qmax);
+      z = -z;
+      if constexpr (DU) {
+        wave_lds_sync();
+        xch[l] = 0.0;
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < MR; ++r)
+          if (pos[r] >= 0) xch[pos[r]] = glt[r];
+        wave_lds_sync();
+        double w = xch[l];
+        double Rc[NL];
+        lds_row16(&R[l * NL], Rc);
+        wave_lds_sync();
+        {
+          const double ninv = -invRd;
+          unroll<NL - 1>([&](auto S) {
+            constexpr int s = S;
+            if (s + 1 < qmax) fmac_bc_nop<s>(w, w * ninv, l > s ? Rc[s] : 0.0);
+          });
+        }
+        w *= invRd;
+        {
+          double nw = -w;
+          pin(nw);
+          dpp_ready(nw);
+          unroll<NL>([&](auto S) {
+            constexpr int s = S;
+            if (s < qmax) fmac_bc<s>(z, nw, Qt[s]);
+          });
+        }
+        cu -= w;
+      }
+      double y;  // dlam of position l
+      {
+        const double ninv = -invRd;
+        double nacc = -cu;
+        unroll<NL>([&](auto JJ) { back_subst_step<NL - 1 - JJ>(R, l, qmax, nacc, ninv); });
+        y = nacc * invRd;
+      }
+      double dx;
+      {
+        const double ninv = -invLd;
+        double nacc = z;
+        unroll<NL>([&](auto JJ) {
+          constexpr int j = NL - 1 - JJ;
+          if (j > 0) {
+            const double lj = l < j ? Lp[lrow(j) + l] : 0.0;
+            fmac_bc_nop<j>(nacc, nacc * ninv, lj);
+          }
+        });
+        dx = nacc * invLd;
+      }
+      wave_lds_sync();
+      xch[l] = y;
+      wave_lds_sync();
+      double dl[MR];
+#pragma unroll
+      for (int r = 0; r < MR; ++r) dl[r] = pos[r] >= 0 ? xch[pos[r]] : 0.0;
+      wave_lds_sync();
+      if (!ok) dx = 0.0;
+      const long long qt = g * (long long)mu.T + t;
+      if (gfg && lives && var) gfg[qt * n + l] = dx;
+#pragma unroll
+      for (int r = 0; r < MR; ++r) {
+        const int row = l + NL * r;
+        if (gbg && lives && row < m) gbg[qt * m + row] = pos[r] >= 0 ? -dl[r] : 0.0;
+      }
+    }
+    return;
+  }
   // (u is projected twice as the rows are: one pass leaves eps |u| of it in the
   // span of Q, which L^{-T} magnifies by up to sqrt(cond H) -- all there is of
   // dx when W leaves little or no freedom; cu sums the two passes' Q^T z)
@@ -611,9 +753,10 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     double *__restrict__ gbg, int n, int m, long long batch, GL... glamg) {
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
-  constexpr bool DU = sizeof...(GL) == 1;
-  static_assert(sizeof...(GL) <= 1 && (std::is_same_v<GL, const double *> && ...) && !(DU && FM == 1),
-                "glam is one array, beside H and A or a buffer of them");
+  constexpr bool MU = tail_is_multi<GL...>;
+  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) == 1;
+  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2),
+                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -643,7 +786,7 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   W = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(W >> 32)) << 32) |
       (unsigned)__builtin_amdgcn_readfirstlane((int)W);
   [[maybe_unused]] double glv = 0.0;  // DU: glam of row `lane`, 0 outside W (whatever it holds there)
-  if constexpr (DU) {
+  if constexpr (DU && !MU) {
     const double v = (glamg, ...)[g * m + (lane < m ? lane : 0)];  // (the form has m > 0)
     glv = ((W >> lane) & 1ull) ? v : 0.0;
   }
@@ -670,7 +813,8 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   posb[lane] = -1.0;
   if (lane < W_COL) colk[lane] = 0.0;
   const bool var = lane < n;
-  double ui = var ? form_gx<FM>(gxg, g * n + lane) : 0.0;  // the running g, u_k = (L^{-1} g)_k from step k on
+  double ui = 0.0;  // the running g, u_k = (L^{-1} g)_k from step k on (MU: per direction, below)
+  if constexpr (!MU) ui = var ? form_gx<FM>(gxg, g * n + lane) : 0.0;
   double invLd = var ? 0.0 : 1.0;                           // 1 / L[lane][lane] (1 on the padding)
   if constexpr (FM == 2) invLd = low ? Hg[fy.ik + lane] : 1.0;
   wave_lds_sync();
@@ -681,7 +825,9 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   // the wave on alternate columns (the upper triangle is redundant and free:
   // no predicate in the loop; the last trip of the upper half may touch the
   // row's padding word, colk is zero there)
-  if constexpr (FM == 2) {
+  if constexpr (MU) {
+    // (every direction's u behind the orthogonalisation, by the loop below)
+  } else if constexpr (FM == 2) {
     // u alone, by the loop's own operations on the stored L and 1 / L_kk
     for (int k = 0; k < n; ++k) {
       const double uk = readlane_d(ui, k) * readlane_d(invLd, k);
@@ -802,6 +948,86 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     }
   }
   wave_lds_sync();
+
+  if constexpr (MU) {
+    // ---- T directions on the one copy of L and orthogonalisation: positions,
+    // 1 / R_tt, Q and R stay in LDS, the vectors region is used again per
+    // direction.  Per direction: the u loop of the factored load on the stored
+    // L, and the statements below from the two projection passes to the stores.
+    const Multi mu = tail_multi(glamg...);
+    const double *__restrict__ gq = gxg + g * mu.stride * n + (var ? lane : 0);
+    [[maybe_unused]] const double *__restrict__ glq = nullptr;
+    if constexpr (DU) glq = tail_glam(glamg...) + g * mu.stride * m + (lane < m ? lane : 0);  // (the form has m > 0)
+    const int p = (int)posb[lane];  // the position of row `lane`, -1: not in W or skipped
+    const double invRd = lane < cnt ? ir[lane] : 0.0;
+    for (int t = 0; t < mu.T; ++t) {
+      const double gl = gq[(long long)t * n];
+      double ut = var ? gl : 0.0;
+      [[maybe_unused]] double glt = 0.0;  // glam of row `lane`, 0 outside W (whatever it holds there)
+      if constexpr (DU) {
+        const double v = glq[(long long)t * m];
+        glt = ((W >> lane) & 1ull) ? v : 0.0;
+      }
+      for (int k = 0; k < n; ++k) {
+        const double uk = readlane_d(ut, k) * readlane_d(invLd, k);
+        const double lik = (low && lane > k) ? Lm[i * WS + k] : 0.0;
+        if (lane == k) ut = uk;
+        else if (low && lane > k) ut = __builtin_fma(-lik, uk, ut);
+      }
+      double z = low ? ut : 0.0, cu = 0.0;
+      project(z, cu);
+      project(z, cu);
+      z = -z;
+      [[maybe_unused]] double wv = 0.0;
+      if constexpr (DU) {
+        wave_lds_sync();
+        if (low) vb[lane] = 0.0;
+        wave_lds_sync();
+        if (p >= 0) vb[p] = glt;
+        wave_lds_sync();
+        wv = lane < cnt ? vb[lane] : 0.0;
+        const double iw = lane < cnt ? ir[lane] : 0.0;
+        for (int s = 0; s < cnt; ++s) {
+          const double wt = readlane_d(wv * iw, s);
+          if (lane == s) wv = wt;
+          else if (lane > s && lane < cnt) wv = __builtin_fma(-Lm[s * WS + lane], wt, wv);
+        }
+        wave_lds_sync();
+        if (low) cb[lane] = wv;
+        wave_lds_sync();
+        if (low) {
+          for (int s0 = 0; s0 < cnt; s0 += 4) {
+#pragma unroll
+            for (int s = s0; s < s0 + 4; ++s) z = __builtin_fma(-cb[s], Qm[s * WS + lane], z);
+          }
+        }
+      }
+      double y = -cu;
+      if constexpr (DU) y += wv;
+      for (int s = cnt - 1; s >= 0; --s) {
+        const double yt = readlane_d(y * invRd, s);
+        if (lane == s) y = yt;
+        else if (lane < s) y = __builtin_fma(-Lm[lane * WS + s], yt, y);
+      }
+      double dx = z;
+#pragma unroll
+      for (int j = WN - 1; j >= 0; --j) {
+        const double dj = readlane_d(dx * invLd, j);
+        const double lj = lane < j ? Lm[j * WS + i] : 0.0;
+        dx = lane == j ? dj : __builtin_fma(-lj, dj, dx);
+      }
+      if (!ok || !var) dx = 0.0;
+      wave_lds_sync();
+      if (low) cb[lane] = lane < cnt ? y : 0.0;
+      wave_lds_sync();
+      const double dl = p >= 0 ? cb[p] : 0.0;
+      const long long qt = g * (long long)mu.T + t;
+      if (gbg && lane < m) gbg[qt * m + lane] = p >= 0 ? -dl : 0.0;
+      if (gfg && var) gfg[qt * n + lane] = dx;
+      wave_lds_sync();  // (the next direction's passes write the vectors again)
+    }
+    return;
+  }
 
   // ---- z = -(u - Q Q^T u), R dlam = -Q^T u, L^T dx = z
   // (two passes, as in the dense kernel)
@@ -1024,6 +1250,40 @@ extern "C" hipError_t qpb_launch_kkt_bwd_factored_dual(const qpb_desc *d, const 
     hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, qpb::bwd::Form<2>>), dim3((unsigned)blocks), dim3(64), 0,
                        stream, bfac, no_a, x, lam, active, status, gx, no_o, gf, no_o, gb, d->n, d->m,
                        (long long)d->batch, glam);
+  });
+  return hipGetLastError();
+}
+
+// qpb_solve_factored_backward_multi: the MU forms of the factored forms, with
+// glam (d->m > 0: the DU MU forms) or without; T directions per QP, the
+// right-hand sides' QP stride in directions rstride (T, or 0: one set for the batch)
+extern "C" hipError_t qpb_launch_kkt_bwd_factored_multi(const qpb_desc *d, const double *bfac, const uint32_t *active,
+                                                        const int32_t *status, int T, long long rstride,
+                                                        const double *gx, const double *glam, double *gf, double *gb,
+                                                        hipStream_t stream) {
+  using qpb::bwd::Form;
+  const qpb::bwd::Multi mu{T, rstride};
+  const double *no_a = nullptr;
+  double *no_o = nullptr;
+  if (d->n > 16 || d->m > 32) {
+    auto go = [&](auto... tail) {
+      hipLaunchKernelGGL((qpb::bwd::kkt_bwd_wave_kernel<false, Form<2>>), dim3((unsigned)d->batch), dim3(64), 0, stream,
+                         bfac, no_a, no_a, no_a, active, status, gx, no_o, gf, no_o, gb, d->n, d->m,
+                         (long long)d->batch, tail...);
+    };
+    if (glam) go(glam, mu);
+    else go(mu);
+    return hipGetLastError();
+  }
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+    auto go = [&](auto... tail) {
+      hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), false, Form<2>>), dim3((unsigned)blocks),
+                         dim3(64), 0, stream, bfac, no_a, no_a, no_a, active, status, gx, no_o, gf, no_o, gb, d->n,
+                         d->m, (long long)d->batch, tail...);
+    };
+    if (glam) go(glam, mu);
+    else go(mu);
   });
   return hipGetLastError();
 }

@@ -70,16 +70,37 @@ __device__ __forceinline__ double sym2(double a, double b, double c, double d) {
 // with r, and every output's formula, as above.  The masked Cholesky is the
 // same; the new work is d, one product of the untouched rows of H with it, and
 // d on the fixed lanes where the other forms store zeros.
+// MU (qpb_solve_box_backward_multi, both kernels, on the SH forms' run-time
+// stride of H, with and without glam): T right-hand sides per QP.  The pack's
+// last argument, a Multi, which only this form has, carries T and the QP stride
+// of the right-hand sides in directions (T, or 0 for one set that the whole
+// batch reads).  Direction t of QP k reads gx + (k stride + t) n and glam +
+// (k stride + t) 2n and writes gf, glb, gub + (k T + t) n.  The load of H, the
+// mask and the masked Cholesky run once; the untouched rows, L, 1 / L_kk and
+// the mask stay where they are, and a loop over t repeats the rest of the
+// single-direction form operation for operation, so every direction's bits
+// are that form's.  x and gH are not arguments of the call: NULL, never read.
+struct Multi {
+  int T;
+  long long stride;
+};
 template <bool SH, class... EX>
 inline constexpr bool extra_pack_ok =
-    SH ? (std::is_same_v<void(EX...), void(long long)> || std::is_same_v<void(EX...), void(long long, const double *)>)
+    SH ? (std::is_same_v<void(EX...), void(long long)> || std::is_same_v<void(EX...), void(long long, const double *)> ||
+          std::is_same_v<void(EX...), void(long long, Multi)> ||
+          std::is_same_v<void(EX...), void(long long, const double *, Multi)>)
        : (std::is_same_v<void(EX...), void()> || std::is_same_v<void(EX...), void(const double *)>);
+template <class... EX>
+inline constexpr bool pack_is_multi = (std::is_same_v<EX, Multi> || ...);
 template <class... T>
 __device__ __forceinline__ long long pack_stride(long long s, T...) {
   return s;
 }
 __device__ __forceinline__ const double *pack_glam(const double *p) { return p; }
 __device__ __forceinline__ const double *pack_glam(long long, const double *p) { return p; }
+__device__ __forceinline__ const double *pack_glam(long long, const double *p, Multi) { return p; }
+__device__ __forceinline__ Multi pack_multi(long long, Multi mu) { return mu; }
+__device__ __forceinline__ Multi pack_multi(long long, const double *, Multi mu) { return mu; }
 
 template <bool N16, bool SH = false, class... EX>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
@@ -87,8 +108,10 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
     double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
     EX... extra) {
-  static_assert(extra_pack_ok<SH, EX...>, "the shared form alone takes the stride, the dual form glam behind it");
-  constexpr bool DU = sizeof...(EX) == (SH ? 2 : 1);
+  static_assert(extra_pack_ok<SH, EX...>,
+                "the shared form alone takes the stride, the dual form glam behind it, the multi form a Multi last");
+  constexpr bool MU = pack_is_multi<EX...>;
+  constexpr bool DU = sizeof...(EX) - (MU ? 1 : 0) == (SH ? 2 : 1);
   __shared__ double lds[QPB * SLOT];
   const int l = threadIdx.x & (NL - 1);
   const int slot = threadIdx.x >> 4;
@@ -111,10 +134,13 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   const uint32_t W = ok ? actg[g] : 0u;
   const uint32_t nmask = (1u << n) - 1u;  // n <= 16
   const uint32_t fixed = (W | (W >> n)) & nmask;
-  const double gv = gxg[g * n + lc];
-  const double xv = xg[g * n + lc];
+  double gv = 0.0, xv = 0.0;  // (MU: per direction, below; no x)
+  if constexpr (!MU) {
+    gv = gxg[g * n + lc];
+    xv = xg[g * n + lc];
+  }
   [[maybe_unused]] double dv = 0.0;  // DU: the prescribed dx of a fixed variable, 0 on a free or padded one
-  if constexpr (DU) {
+  if constexpr (DU && !MU) {
     // both entries are loaded and one is selected: whatever glam holds at a
     // clear bit, NaN included, goes nowhere
     const double *__restrict__ glq = pack_glam(extra...) + g * (long long)(2 * n);
@@ -174,6 +200,47 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_box_dense_kernel(
   });
   __builtin_amdgcn_sched_barrier(0);
   store_l(Lp, l, Lr);  // for the second solve
+
+  if constexpr (MU) {
+    // ---- T directions on the one factorisation: the statements below, from
+    // the loads of gx and glam to the three stores, once per direction
+    const Multi mu = pack_multi(extra...);
+    const double *__restrict__ gq = gxg + g * mu.stride * n + lc;
+    [[maybe_unused]] const double *__restrict__ glq = nullptr;
+    if constexpr (DU) glq = pack_glam(extra...) + g * mu.stride * (2 * n) + lc;
+    const long long o0 = g * (long long)mu.T * n + l;
+    const bool bu = var && ((W >> l) & 1u), bl = var && ((W >> (l + n)) & 1u);
+    const bool up = (W >> l) & 1u, lo = (W >> (l + n)) & 1u;
+    for (int t = 0; t < mu.T; ++t) {
+      const double gt = gq[(long long)t * n];
+      [[maybe_unused]] double dt = 0.0;
+      if constexpr (DU) {
+        const double gu = glq[(long long)t * (2 * n)], gw = glq[(long long)t * (2 * n) + n];
+        dt = bu ? -gu : (bl ? gw : 0.0);
+      }
+      double rhs = gt;
+      if constexpr (DU) {
+        pin(dt);
+        dpp_ready(dt);
+        unroll<NL>([&](auto K) { fmac_bc<K>(rhs, dt, Hr[K]); });
+      }
+      double dx = solve_x(fix ? 0.0 : rhs, invLd, Lr, Lp, l, xcap);
+      if (fix || !ok) dx = 0.0;
+      if constexpr (DU) dx = fix ? dt : dx;
+      double r = gt;
+      pin(dx);
+      dpp_ready(dx);
+      unroll<NL>([&](auto K) { fmac_bc<K>(r, dx, Hr[K]); });
+      if (live && var) {
+        const long long o = o0 + (long long)t * n;
+        if (gfg) gfg[o] = dx;
+        if (gubg) gubg[o] = up ? r : 0.0;
+        if (glbg) glbg[o] = (lo && !up) ? r : 0.0;
+      }
+      wave_lds_sync();  // (the next direction's solves write the captured components again)
+    }
+    return;
+  }
 
   // ---- dx = -H~^{-1} g~: exact zeros on the fixed lanes
   double rhs = gv;
@@ -254,8 +321,10 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
     const int32_t *__restrict__ statg, const double *__restrict__ gxg, double *__restrict__ gHg,
     double *__restrict__ gfg, double *__restrict__ glbg, double *__restrict__ gubg, int n, long long batch,
     EX... extra) {
-  static_assert(extra_pack_ok<SH, EX...>, "the shared form alone takes the stride, the dual form glam behind it");
-  constexpr bool DU = sizeof...(EX) == (SH ? 2 : 1);
+  static_assert(extra_pack_ok<SH, EX...>,
+                "the shared form alone takes the stride, the dual form glam behind it, the multi form a Multi last");
+  constexpr bool MU = pack_is_multi<EX...>;
+  constexpr bool DU = sizeof...(EX) - (MU ? 1 : 0) == (SH ? 2 : 1);
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -295,9 +364,10 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
   if (lane < W_COL) colk[lane] = 0.0;
   const bool var = lane < n;
   const bool fix = !var || ((fixed >> i) & 1u);  // (lane < n <= 32: i == lane)
-  const double gv = var ? gxg[g * n + lane] : 0.0;
+  double gv = 0.0;  // (MU: per direction, below)
+  if constexpr (!MU) gv = var ? gxg[g * n + lane] : 0.0;
   [[maybe_unused]] double dv = 0.0;  // DU: the prescribed dx of a fixed variable, 0 on a free or padded one
-  if constexpr (DU) {
+  if constexpr (DU && !MU) {
     // both entries are loaded and one is selected: whatever glam holds at a
     // clear bit, NaN included, goes nowhere
     const double *__restrict__ glq = pack_glam(extra...) + g * (long long)(2 * n);
@@ -310,6 +380,93 @@ __global__ __launch_bounds__(64) void kkt_bwd_box_wave_kernel(
   double ui = fix ? 0.0 : gv;       // the running g~, u_k = (L^{-1} g~)_k from step k on
   double invLd = var ? 0.0 : 1.0;   // 1 / L[lane][lane] (1 on the padding)
   wave_lds_sync();
+  if constexpr (MU) {
+    // ---- H~ = L L^T alone, by the loop below without its u; then T directions
+    // on it.  A direction takes u = L^{-1} g~ from the stored L and 1 / L_kk by
+    // that loop's own operations on u (as kkt_bwd_wave_kernel does on a factor
+    // buffer), and the rest is the single-direction form's, statement for
+    // statement, from the loads of gx and glam to the three stores.
+    for (int k = 0; k < n; ++k) {
+      const double ik = rsq(Lm[k * WS + k]);
+      const double lik = i >= k ? Lm[i * WS + k] * ik : 0.0;
+      wave_lds_sync();
+      if (half == 0) {
+        colk[i] = i > k ? lik : 0.0;
+        if (i >= k) Lm[i * WS + k] = lik;
+      }
+      if (lane == k) invLd = ik;
+      wave_lds_sync();
+      const double nl = i > k ? -lik : 0.0;
+      double *row = Lm + i * WS + k + 1 + half;
+      const double *col = colk + k + 1 + half;
+      const int trips = (WN - k) / 2;
+#pragma unroll 4
+      for (int jj = 0; jj < trips; ++jj) row[2 * jj] = __builtin_fma(nl, col[2 * jj], row[2 * jj]);
+      wave_lds_sync();
+    }
+    const Multi mu = pack_multi(extra...);
+    const int lc = var ? lane : 0;
+    const double *__restrict__ gq = gxg + g * mu.stride * n + lc;
+    [[maybe_unused]] const double *__restrict__ glq = nullptr;
+    if constexpr (DU) glq = pack_glam(extra...) + g * mu.stride * (2 * n) + lc;
+    const bool up = (upw >> i) & 1u, lo = (low_w >> i) & 1u;  // (used on lanes < n: i == lane)
+    for (int t = 0; t < mu.T; ++t) {
+      const double gl = gq[(long long)t * n];
+      const double gt = var ? gl : 0.0;
+      [[maybe_unused]] double dt = 0.0;
+      if constexpr (DU) {
+        const double gu = glq[(long long)t * (2 * n)], gw = glq[(long long)t * (2 * n) + n];
+        dt = (var && up) ? -gu : ((var && lo) ? gw : 0.0);
+        if (low) DX[lane] = dt;
+        wave_lds_sync();
+      }
+      double ut = fix ? 0.0 : gt;
+      if constexpr (DU) {
+        if (!fix) {
+          double r0 = gt, r1 = 0.0;
+#pragma unroll
+          for (int j = 0; j < WN; j += 2) {
+            r0 = __builtin_fma(Hm[lane * WS + j], DX[j], r0);
+            r1 = __builtin_fma(Hm[lane * WS + j + 1], DX[j + 1], r1);
+          }
+          ut = r0 + r1;
+        }
+      }
+      for (int k = 0; k < n; ++k) {
+        const double uk = readlane_d(ut, k) * readlane_d(invLd, k);
+        const double lik = (low && lane > k) ? Lm[i * WS + k] : 0.0;
+        if (lane == k) ut = uk;
+        else if (low && lane > k) ut = __builtin_fma(-lik, uk, ut);
+      }
+      double dx = low ? -ut : 0.0;
+#pragma unroll
+      for (int j = WN - 1; j >= 0; --j) {
+        const double dj = readlane_d(dx * invLd, j);
+        const double lj = lane < j ? Lm[j * WS + i] : 0.0;
+        dx = lane == j ? dj : __builtin_fma(-lj, dj, dx);
+      }
+      if (!ok || fix) dx = 0.0;
+      if constexpr (DU) dx = fix ? dt : dx;
+      wave_lds_sync();
+      if (low) DX[lane] = dx;
+      wave_lds_sync();
+      if (var) {
+        double r0 = gt, r1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < WN; j += 2) {
+          r0 = __builtin_fma(Hm[lane * WS + j], DX[j], r0);
+          r1 = __builtin_fma(Hm[lane * WS + j + 1], DX[j + 1], r1);
+        }
+        const double r = r0 + r1;
+        const long long o = (g * (long long)mu.T + t) * n + lane;
+        if (gfg) gfg[o] = dx;
+        if (gubg) gubg[o] = up ? r : 0.0;
+        if (glbg) glbg[o] = (lo && !up) ? r : 0.0;
+      }
+      wave_lds_sync();  // (the next direction writes DX again)
+    }
+    return;
+  }
   if constexpr (DU) {
     // g~_F = g_F + H_FS d_S: d is zero off S, so the whole untouched row
     // serves, by the loop of r below
@@ -468,5 +625,35 @@ extern "C" hipError_t qpb_launch_kkt_bwd_box_dual(const qpb_desc *d, long long s
   else
     hipLaunchKernelGGL((kkt_bwd_box_dense_kernel<false, false, const double *>), dim3((unsigned)blocks), dim3(64), 0,
                        stream, H, x, active, status, gx, gH, gf, glb, gub, d->n, (long long)d->batch, glam);
+  return hipGetLastError();
+}
+
+// qpb_solve_box_backward_multi: the MU forms on H's run-time stride (0 or n n),
+// with glam (the DU MU forms) or without; T directions per QP, the right-hand
+// sides' QP stride in directions rstride (T, or 0: one set for the batch)
+extern "C" hipError_t qpb_launch_kkt_bwd_box_multi(const qpb_desc *d, long long strideH, const double *H,
+                                                   const uint32_t *active, const int32_t *status, int T,
+                                                   long long rstride, const double *gx, const double *glam,
+                                                   double *gf, double *glb, double *gub, hipStream_t stream) {
+  using namespace qpb::bwdbox;
+  const Multi mu{T, rstride};
+  const double *no_x = nullptr;
+  double *no_h = nullptr;
+  const long long blocks = (d->batch + QPB - 1) / QPB;
+  const dim3 grid((unsigned)(d->n > 16 ? d->batch : blocks));
+  auto go = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, H, no_x, active, status, gx, no_h, gf, glb, gub, d->n,
+                       (long long)d->batch, strideH, tail...);
+  };
+  if (d->n > 16) {
+    if (glam) go(kkt_bwd_box_wave_kernel<true, long long, const double *, Multi>, glam, mu);
+    else go(kkt_bwd_box_wave_kernel<true, long long, Multi>, mu);
+  } else if (d->n == 16) {
+    if (glam) go(kkt_bwd_box_dense_kernel<true, true, long long, const double *, Multi>, glam, mu);
+    else go(kkt_bwd_box_dense_kernel<true, true, long long, Multi>, mu);
+  } else {
+    if (glam) go(kkt_bwd_box_dense_kernel<false, true, long long, const double *, Multi>, glam, mu);
+    else go(kkt_bwd_box_dense_kernel<false, true, long long, Multi>, mu);
+  }
   return hipGetLastError();
 }

@@ -150,6 +150,20 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box_dual(const qpb_desc *d, long long
                                                     const double *x, const uint32_t *active, const int32_t *status,
                                                     const double *gx, const double *glam, double *gH, double *gf,
                                                     double *glb, double *gub, hipStream_t stream);
+// qpb_solve_factored_backward_multi: the MU forms of the factored forms (glam
+// NULL or d->m == 0: without the DU steps).  T right-hand sides per QP,
+// direction-major; rstride is their QP stride in directions: T, or 0 for one
+// set (T x n, T x m) that every QP reads.  gf is batch x T x n, gb batch x T x m.
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_factored_multi(const qpb_desc *d, const double *bfac,
+                                                          const uint32_t *active, const int32_t *status, int T,
+                                                          long long rstride, const double *gx, const double *glam,
+                                                          double *gf, double *gb, hipStream_t stream);
+// qpb_solve_box_backward_multi: the MU forms of the box kernels on H's run-time
+// stride (0 or n n), glam (T x 2n per QP) NULL or not; gf, glb, gub batch x T x n
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_box_multi(const qpb_desc *d, long long strideH, const double *H,
+                                                     const uint32_t *active, const int32_t *status, int T,
+                                                     long long rstride, const double *gx, const double *glam,
+                                                     double *gf, double *glb, double *gub, hipStream_t stream);
 // with per-section wave ticks into sections[256][20] (the stamped diagnostic builds)
 typedef hipError_t qpb_gi_sections_launcher(const qpb_desc *d, const double *H, const double *f, const double *A,
                                             const double *b, double *x, double *lam, uint32_t *active,

@@ -327,6 +327,49 @@ static_assert(route_bwd_box_dual(kBwdBoxDualMaxN).step > 0 && route_bwd_box_dual
 static_assert(route_bwd_box_dual(16).kernel == route(16, 32, 0, true).kernel &&
               route_bwd_box_dual(17).kernel == route(17, 34, 0, true).kernel);
 
+// qpb_solve_factored_backward_multi and qpb_solve_box_backward_multi: the
+// single-direction dual routes' classes, whose MU forms loop over T right-hand
+// sides per QP, and their steps (a chunk is `step` QPs whatever T is: the
+// kernels' grids count QPs); above them there is none: step 0, and the calls
+// are unsupported.
+constexpr Route route_factored_bwd_multi(int n, int m) {
+  const Route r = route_factored_bwd_dual(n, m);
+  return {r.kernel, r.step};
+}
+constexpr Route route_bwd_box_multi(int n) { return route_bwd_box_dual(n); }
+constexpr int kBwdMultiMaxN = kFactoredBwdDualMaxN, kBwdMultiMaxM = kFactoredBwdDualMaxM;
+constexpr int kBwdBoxMultiMaxN = kBwdBoxDualMaxN;
+constexpr int kMaxRhs = 256;  // QPB_MAX_RHS: every column of K^-1 at the largest shape in one call
+
+static_assert(route_factored_bwd_multi(1, 0).kernel == Kernel::gi_dense &&
+              route_factored_bwd_multi(16, 32).kernel == Kernel::gi_dense);
+static_assert(route_factored_bwd_multi(16, 33).kernel == Kernel::gi_wave &&
+              route_factored_bwd_multi(17, 0).kernel == Kernel::gi_wave &&
+              route_factored_bwd_multi(32, 64).kernel == Kernel::gi_wave);
+// each direction's bits are the single-direction call's on the same buffer: its classes and steps
+static_assert(route_factored_bwd_multi(16, 32).kernel == route_factored_bwd_dual(16, 32).kernel &&
+              route_factored_bwd_multi(16, 32).step == route_factored_bwd_dual(16, 32).step &&
+              route_factored_bwd_multi(32, 64).kernel == route_factored_bwd_dual(32, 64).kernel &&
+              route_factored_bwd_multi(32, 64).step == route_factored_bwd_dual(32, 64).step);
+static_assert(route_factored_bwd_multi(33, 0).step == 0 && route_factored_bwd_multi(16, 65).step == 0 &&
+              route_factored_bwd_multi(128, 256).step == 0);
+static_assert(route_factored_bwd_multi(kBwdMultiMaxN, kBwdMultiMaxM).step > 0 &&
+              route_factored_bwd_multi(kBwdMultiMaxN + 1, 1).step == 0 &&
+              route_factored_bwd_multi(1, kBwdMultiMaxM + 1).step == 0);
+static_assert(route_bwd_box_multi(1).kernel == Kernel::gi_box && route_bwd_box_multi(16).kernel == Kernel::gi_box);
+static_assert(route_bwd_box_multi(17).kernel == Kernel::gi_wave_box &&
+              route_bwd_box_multi(32).kernel == Kernel::gi_wave_box);
+static_assert(route_bwd_box_multi(16).kernel == route_bwd_box_dual(16).kernel &&
+              route_bwd_box_multi(16).step == route_bwd_box_dual(16).step &&
+              route_bwd_box_multi(32).kernel == route_bwd_box_dual(32).kernel &&
+              route_bwd_box_multi(32).step == route_bwd_box_dual(32).step);
+static_assert(route_bwd_box_multi(33).step == 0 && route_bwd_box_multi(128).step == 0);
+static_assert(route_bwd_box_multi(kBwdBoxMultiMaxN).step > 0 && route_bwd_box_multi(kBwdBoxMultiMaxN + 1).step == 0);
+// every column of K^-1 in one call: n + m right-hand sides at the largest shape
+static_assert(kMaxRhs >= kBwdMultiMaxN + kBwdMultiMaxM && kMaxRhs >= 3 * kBwdBoxMultiMaxN);
+// a chunk's largest element offset, step QPs of kMaxRhs directions of m doubles, is far inside 63 bits
+static_assert(route_factored_bwd_multi(16, 32).step <= (1LL << 62) / (kMaxRhs * kBwdMultiMaxM));
+
 // qpb_solve_range with m > 0: the RG forms of the two wavefront-level classes,
 // whatever meq and the shared bits (the forms take both at run time); above
 // them -- the Gram class -- there is no range form yet: step 0, and the call is

@@ -56,6 +56,8 @@ FLAG_DIAG_L2, FLAG_DIAG_MALL = 1, 16
 FLAG_MIXED, FLAG_DIAG_NO_REDO = 32, 64
 # the `shared` argument of qpb_solve_shared / qpb_solve_shared_backward
 SHARED_H, SHARED_A = 1, 2
+SHARED_RHS = 4  # the *_multi calls: gx and glam are ONE set of T right-hand sides for the whole batch
+MAX_RHS = 256
 FLAG_DIAG_WAVE = 256  # n <= 16 solved by the one-QP-per-wavefront kernel (lockstep endpoint; measurement only)
 STATUS_REDO = 100  # internal: a QP the mixed kernel leaves to the fp64 re-solve (FLAG_DIAG_NO_REDO only)
 
@@ -146,6 +148,17 @@ _lib.qpb_solve_box_backward_dual.argtypes = [ctypes.POINTER(Desc), ctypes.c_int3
 _lib.qpb_solve_box_backward_dual.restype = ctypes.c_int
 _lib.qpb_solve_box_backward_dual_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
 _lib.qpb_solve_box_backward_dual_host.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward_multi.argtypes = [ctypes.POINTER(Desc)] + [_vp] * 3 + [ctypes.c_int32] * 2 + [_vp] * 5
+_lib.qpb_solve_factored_backward_multi.restype = ctypes.c_int
+_lib.qpb_solve_factored_backward_multi_host.argtypes = ([ctypes.POINTER(Desc)] + [_vp] * 3 + [ctypes.c_int32] * 2
+                                                        + [_vp] * 4)
+_lib.qpb_solve_factored_backward_multi_host.restype = ctypes.c_int
+_lib.qpb_solve_box_backward_multi.argtypes = ([ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 3 + [ctypes.c_int32]
+                                              + [_vp] * 6)
+_lib.qpb_solve_box_backward_multi.restype = ctypes.c_int
+_lib.qpb_solve_box_backward_multi_host.argtypes = ([ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 3
+                                                   + [ctypes.c_int32] + [_vp] * 5)
+_lib.qpb_solve_box_backward_multi_host.restype = ctypes.c_int
 _lib.qpb_factor_box_doubles.argtypes = [ctypes.c_int32]
 _lib.qpb_factor_box_doubles.restype = ctypes.c_int64
 _lib.qpb_factor_box.argtypes = [ctypes.c_int32] + [_vp] * 4
@@ -1533,6 +1546,231 @@ def solve_box_tangent(H, sol: Solution, df, dlb=None, dub=None, *, stream=None):
             glam = torch.cat((z if dub is None else -dub, z if dlb is None else dlb), dim=1).contiguous()
         _, dx, glb, gub = solve_box_backward_dual(H, sol, df, glam, need=("f", "lb", "ub"), stream=stream)
         return dx, torch.cat((-gub, glb), dim=1)
+
+
+# ---- T right-hand sides per QP in one launch -----------------------------------
+MULTI_NEED_ALL = ("f", "b")
+BOX_MULTI_NEED_ALL = ("f", "lb", "ub")
+
+
+def _multi_need_set(need, names) -> set:
+    need = set(need)
+    if not need or not need <= set(names):
+        raise ValueError(f"need must be a non-empty subset of {names}")
+    return need
+
+
+def _multi_dims(gx, n: int, B: int):
+    """(T, shared bit) of right-hand sides (B, T, n), or (T, n) for one set that
+    every QP reads."""
+    if gx.ndim == 3 and tuple(gx.shape[::2]) == (B, n):
+        T, sh = int(gx.shape[1]), 0
+    elif gx.ndim == 2 and gx.shape[1] == n:
+        T, sh = int(gx.shape[0]), SHARED_RHS
+    else:
+        raise ValueError(f"shape mismatch: gx must be (B, T, n) or (T, n) with B={B}, n={n}")
+    if not 1 <= T <= MAX_RHS:
+        raise ValueError(f"the number of right-hand sides T must be 1..{MAX_RHS} (got {T})")
+    return T, sh
+
+
+def _multi_sol_batch(sol: Solution) -> int:
+    lead = sol.active if sol.active is not None else sol.status
+    if lead is None:
+        raise ValueError("sol.active or sol.status must give the batch size")
+    return int(lead.shape[0])
+
+
+def _multi_check_sol_cuda(sol: Solution, B: int, words: int, dev):
+    import torch
+    if words and (sol.active is None or not sol.active.is_cuda or not sol.active.is_contiguous()
+                  or tuple(sol.active.shape) != (B, words) or sol.active.element_size() != 4
+                  or sol.active.device != dev):
+        raise ValueError("sol.active must be a contiguous (B, ceil(m/32)) CUDA tensor of 32-bit words")
+    if sol.status is not None and (not sol.status.is_cuda or sol.status.dtype != torch.int32
+                                   or not sol.status.is_contiguous() or tuple(sol.status.shape) != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+
+
+def solve_factored_backward_multi(F: BackwardFactor, sol: Solution, gx, glam=None, *, need=MULTI_NEED_ALL,
+                                  stream=None):
+    """T right-hand sides per QP in ONE launch (qpb_solve_factored_backward_multi):
+    ``solve_factored_backward_dual(F, sol, gx[:, t], glam[:, t], need=("f", "b"))``
+    for every direction t, bit for bit, with the factored load and the
+    orthogonalisation done once per QP.  ``gx`` is (B, T, n) and ``glam``
+    (B, T, m), or (T, n) and (T, m) for ONE set that every QP reads (B is taken
+    from ``sol.active`` / ``sol.status``).  Returns (gf (B, T, n), gb (B, T, m));
+    an entry is None where ``need`` leaves it out, and gb with m == 0.  Only
+    ``sol.active`` and ``sol.status`` are read.  ``glam=None`` (or m = 0) is
+    ``solve_factored_backward`` per direction.  n <= 32, m <= 64, T <= 256."""
+    import torch
+    if not (gx.is_cuda and F.fac.is_cuda):
+        raise ValueError("qpb.solve_factored_backward_multi expects CUDA (HIP) tensors; "
+                         "use solve_factored_backward_multi_host for numpy")
+    n, m = int(F.n), int(F.m)
+    need = _multi_need_set(need, MULTI_NEED_ALL)
+    if gx.dtype != torch.float64 or not gx.is_contiguous():
+        raise ValueError("inputs must be contiguous float64")
+    B = _multi_sol_batch(sol)
+    T, shared = _multi_dims(gx, n, B)
+    if F.fac.dtype != torch.float64 or tuple(F.fac.shape) != (factor_backward_doubles(n, m),) \
+            or not F.fac.is_contiguous():
+        raise ValueError(f"the backward factor buffer is not one for n={n}, m={m}")
+    if F.fac.device != gx.device:
+        raise ValueError("the inputs must live on the factor's CUDA device")
+    _multi_check_sol_cuda(sol, B, (m + 31) // 32, gx.device)
+    if glam is not None and (not glam.is_cuda or glam.dtype != torch.float64 or not glam.is_contiguous()
+                             or glam.device != gx.device or tuple(glam.shape) != tuple(gx.shape[:-1]) + (m,)):
+        raise ValueError("glam must be a contiguous float64 CUDA tensor of gx's shape with m in place of n, or None")
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=gx.device)  # noqa: E731
+    gf = new(B, T, n) if "f" in need else None
+    gb = new(B, T, m) if m and "b" in need else None
+    if gf is None and gb is None:
+        return None, None  # m == 0 and only b wanted
+    d = Desc(n, m, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_factored_backward_multi(ctypes.byref(d), _ptr(F.fac), _ptr(sol.active) if m else None,
+                                                _ptr(sol.status), T, shared, _ptr(gx),
+                                                _ptr(glam) if m and glam is not None else None, _ptr(gf), _ptr(gb),
+                                                _stream_ptr(stream))
+    _check(rc, "qpb_solve_factored_backward_multi")
+    return gf, gb
+
+
+def solve_factored_tangents(F: BackwardFactor, sol: Solution, df, db=None, *, stream=None):
+    """``solve_factored_tangent`` for T directions in ONE launch: the tangents
+    ``(dx, dlam)`` of (x*, lam*) along ``df`` (B, T, n) and ``db`` (B, T, m) --
+    or (T, n) and (T, m) for directions that do not depend on the QP, the
+    columns of an affine law -- at fixed active set: ``gx = df``,
+    ``glam = -db``, ``dlam = -gb``.  Returns dx (B, T, n) and dlam (B, T, m)
+    (None at m = 0), each direction bit for bit ``solve_factored_tangent``'s."""
+    import contextlib
+
+    import torch
+    m = int(F.m)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        glam = None if db is None or not m else -db
+        dx, gb = solve_factored_backward_multi(F, sol, df, glam, need=("f", "b"), stream=stream)
+        return dx, (None if gb is None else -gb)
+
+
+def solve_factored_backward_multi_host(F: BackwardFactor, sol: Solution, gx, glam=None, *, need=MULTI_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_factored_backward_multi_host): ``solve_factored_backward_multi`` with host
+    arrays."""
+    import numpy as np
+    need = _multi_need_set(need, MULTI_NEED_ALL)
+    n, m = int(F.n), int(F.m)
+    fac = np.ascontiguousarray(F.fac, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    B = _multi_sol_batch(sol)
+    T, shared = _multi_dims(gx, n, B)
+    act = None
+    if m:
+        act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    if fac.shape != (factor_backward_doubles(n, m),) or (m and act.shape != (B, (m + 31) // 32)):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    glam = None if glam is None or not m else np.ascontiguousarray(glam, dtype=np.float64)
+    if glam is not None and glam.shape != gx.shape[:-1] + (m,):
+        raise ValueError(f"shape mismatch: the factor is for n={n}, m={m}")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    if st is not None and st.shape != (B,):
+        raise ValueError("shape mismatch: sol.status must be (B,)")
+    gf = np.zeros((B, T, n)) if "f" in need else None
+    gb = np.zeros((B, T, m)) if m and "b" in need else None
+    if gf is None and gb is None:
+        return None, None
+    d = Desc(n, m, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_factored_backward_multi_host(ctypes.byref(d), p(fac), p(act), p(st), T, shared, p(gx),
+                                                     p(glam), p(gf), p(gb))
+    _check(rc, "qpb_solve_factored_backward_multi_host")
+    return gf, gb
+
+
+def solve_box_backward_multi(H, sol: Solution, gx, glam=None, *, need=BOX_MULTI_NEED_ALL, stream=None):
+    """T right-hand sides per QP in ONE launch (qpb_solve_box_backward_multi):
+    ``solve_box_backward_dual(H, sol, gx[:, t], glam[:, t], need=("f", "lb",
+    "ub"))`` for every direction t, bit for bit, with H loaded and the masked
+    Cholesky done once per QP.  H is (B, n, n), or (n, n) for one H; ``gx`` is
+    (B, T, n) and ``glam`` (B, T, 2n), or (T, n) and (T, 2n) for ONE set that
+    every QP reads (B is taken from ``sol.active``).  Returns (gf, glb, gub),
+    each (B, T, n), None where ``need`` leaves it out.  Only ``sol.active`` and
+    ``sol.status`` are read.  ``glam=None`` is ``solve_box_backward`` per
+    direction.  n <= 32, T <= 256."""
+    import torch
+    if not (H.is_cuda and gx.is_cuda):
+        raise ValueError("qpb.solve_box_backward_multi expects CUDA (HIP) tensors; "
+                         "use solve_box_backward_multi_host for numpy")
+    for t in (H, gx) + (() if glam is None else (glam,)):
+        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous float64 CUDA tensors")
+    n = int(H.shape[-1])
+    B = _multi_sol_batch(sol)
+    T, shared = _multi_dims(gx, n, B)
+    if H.dim() == 2:
+        shared |= SHARED_H
+    if tuple(H.shape) != ((n, n) if H.dim() == 2 else (B, n, n)) \
+            or (glam is not None and tuple(glam.shape) != tuple(gx.shape[:-1]) + (2 * n,)):
+        raise ValueError("shape mismatch: H must be (n, n) or (B, n, n) and glam gx's shape with 2n in place of n")
+    need = _multi_need_set(need, BOX_MULTI_NEED_ALL)
+    _multi_check_sol_cuda(sol, B, (2 * n + 31) // 32, gx.device)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=gx.device)  # noqa: E731
+    gf = new(B, T, n) if "f" in need else None
+    glb = new(B, T, n) if "lb" in need else None
+    gub = new(B, T, n) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_box_backward_multi(ctypes.byref(d), shared, _ptr(H), _ptr(sol.active), _ptr(sol.status), T,
+                                           _ptr(gx), _ptr(glam), _ptr(gf), _ptr(glb), _ptr(gub), _stream_ptr(stream))
+    _check(rc, "qpb_solve_box_backward_multi")
+    return gf, glb, gub
+
+
+def solve_box_tangents(H, sol: Solution, df, dlb=None, dub=None, *, stream=None):
+    """``solve_box_tangent`` for T directions in ONE launch: the tangents
+    ``(dx, dlam)`` of (x*, lam*) along ``df``, ``dlb`` and ``dub``, each
+    (B, T, n) or, for directions that do not depend on the QP, (T, n); ``dlam``
+    is (B, T, 2n) in ``solve_box``'s lam layout.  ``gx = df``,
+    ``glam[..., :n] = -dub``, ``glam[..., n:] = +dlb``, ``dx = gf``,
+    ``dlam = [-gub, +glb]``: each direction bit for bit ``solve_box_tangent``'s."""
+    import contextlib
+
+    import torch
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        glam = None
+        if dlb is not None or dub is not None:
+            z = torch.zeros_like(df)
+            glam = torch.cat((z if dub is None else -dub, z if dlb is None else dlb), dim=-1).contiguous()
+        dx, glb, gub = solve_box_backward_multi(H, sol, df, glam, need=("f", "lb", "ub"), stream=stream)
+        return dx, torch.cat((-gub, glb), dim=-1)
+
+
+def solve_box_backward_multi_host(H, sol: Solution, gx, glam=None, *, need=BOX_MULTI_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_box_backward_multi_host): ``solve_box_backward_multi`` with host arrays."""
+    import numpy as np
+    need = _multi_need_set(need, BOX_MULTI_NEED_ALL)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    gx = np.ascontiguousarray(gx, dtype=np.float64)
+    n = H.shape[-1]
+    B = _multi_sol_batch(sol)
+    T, shared = _multi_dims(gx, n, B)
+    if H.ndim == 2:
+        shared |= SHARED_H
+    act = np.ascontiguousarray(np.asarray(sol.active).astype(np.uint32))
+    glam = None if glam is None else np.ascontiguousarray(glam, dtype=np.float64)
+    if H.shape != ((n, n) if H.ndim == 2 else (B, n, n)) or act.shape != (B, (2 * n + 31) // 32) \
+            or (glam is not None and glam.shape != gx.shape[:-1] + (2 * n,)):
+        raise ValueError("shape mismatch")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    if st is not None and st.shape != (B,):
+        raise ValueError("shape mismatch: sol.status must be (B,)")
+    gf = np.zeros((B, T, n)) if "f" in need else None
+    glb = np.zeros((B, T, n)) if "lb" in need else None
+    gub = np.zeros((B, T, n)) if "ub" in need else None
+    d = Desc(n, 2 * n, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_box_backward_multi_host(ctypes.byref(d), shared, p(H), p(act), p(st), T, p(gx), p(glam),
+                                                p(gf), p(glb), p(gub))
+    _check(rc, "qpb_solve_box_backward_multi_host")
+    return gf, glb, gub
 
 
 def active_mask_to_bool(active, m: int):

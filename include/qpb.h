@@ -23,6 +23,7 @@
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
  *   ... differentiated on the H and A factored once           qpb_factor_shared_backward, qpb_solve_factored_backward
  *   ... that, and the box backward, for a loss that reads lam  qpb_solve_factored_backward_dual, qpb_solve_box_backward_dual
+ *   ... those two for T right-hand sides per QP in one launch    qpb_solve_factored_backward_multi, qpb_solve_box_backward_multi
  *   (absent from the reference: SURVEY.md §0)
  *   qp.h:19-24         quadratic_form_eval / _eval_grad  qpb_qf_eval
  *
@@ -1091,6 +1092,98 @@ int qpb_solve_box_factored_host(const qpb_desc *desc, const double *bxfac,
 				const double *ub, double *x, double *lam,
 				uint32_t *active, int32_t *status,
 				int32_t *iters);
+
+/* T right-hand sides per QP in ONE launch: qpb_solve_factored_backward_dual
+ * (gH = gA = NULL) and qpb_solve_box_backward_dual (gH = NULL) for T = nrhs
+ * directions (gx, glam) at a time.  Because K is symmetric these are also T
+ * tangents of (x*, lam*): the columns of a Jacobian dx* / df (gx = I), or of
+ * the local affine law of an MPC tick.  Everything that does
+ * not depend on the right-hand side -- the load of the buffer or of H, the
+ * orthogonalisation D_W^T = Q R, the masked Cholesky -- runs once per QP; one
+ * more direction costs the projections and the triangular solves.
+ *
+ * Layouts.  The right-hand sides of QP k are contiguous and direction-major:
+ * direction t is at gx + (k T + t) n and glam + (k T + t) m (m = 2n for the box
+ * call).  The outputs likewise: gf is B x T x n, gb B x T x m, glb and gub
+ * B x T x n.  T = 1 gives the single-direction calls' layouts.
+ *   QPB_SHARED_RHS  gx is T x n and glam T x m: ONE set of right-hand sides
+ *                   that every QP reads (df = F e_j, db = G e_j of the affine
+ *                   law; gx = I of the Jacobian).  The outputs equal those on
+ *                   B materialised copies bit for bit.
+ *   QPB_SHARED_H    box call only, as in qpb_solve_box_backward_dual: ONE
+ *                   n x n H.
+ * x and lam are not arguments: neither gf nor gb depends on them.  There is no
+ * gH or gA: they are outer products with one x; the single-direction calls
+ * have them.
+ *
+ * Contract.  For every QP k and direction t the outputs of direction t equal
+ * BIT FOR BIT what the single-direction call writes into the same outputs for
+ * that QP with gx[k, t] and glam[k, t]: qpb_solve_factored_backward_dual on the
+ * same buffer, active and status, qpb_solve_box_backward_dual on the same H,
+ * shared & QPB_SHARED_H, active and status.  Each direction runs the same
+ * operations on the same numbers in the same order.  Everything those calls
+ * say holds per direction: the glam of a row outside W, of a skipped row, of a
+ * clear bit and of a QP that is not QPB_OK is ignored, NaN included; such a QP,
+ * and every QP on a buffer whose H was not positive definite, gets zeros in
+ * every direction; both bits of a box variable set: the upper bound counts;
+ * bits >= m (>= 2n) are ignored; dx is -+glam exactly on a fixed box variable;
+ * status == NULL counts as QPB_OK; every element of every non-NULL output is
+ * written and nothing else; a QP's outputs depend on its own inputs only.
+ * And: direction t's outputs depend on direction t's right-hand side only --
+ * not on T, on t, or on what the other directions hold, NaN included.
+ *   glam == NULL    (or m == 0 in the factored call) the forms without the DU
+ *                   steps: each direction is qpb_solve_factored_backward's or
+ *                   qpb_solve_box_backward's bit for bit.
+ *   m == 0          gb is ignored.
+ *   outputs         each may be NULL; at least one must be given.
+ * The kernels are the MU forms of qpb_kkt_bwd.hip's factored forms and of
+ * qpb_kkt_bwd_box.hip's kernels.
+ * Errors, in order: the descriptor as qpb_solve; box call: m != 2n
+ * QPB_ERR_INVALID_ARG; flags != 0, a bit of `shared` outside QPB_SHARED_RHS
+ * (box call: QPB_SHARED_H | QPB_SHARED_RHS), nrhs < 1 or > QPB_MAX_RHS
+ * QPB_ERR_INVALID_ARG; n > 32 or m > 64 QPB_ERR_UNSUPPORTED; batch == 0
+ * returns 0 before the pointers are looked at; missing pointers
+ * QPB_ERR_INVALID_ARG (bfac or H, gx, active -- factored call: when m > 0 --
+ * and at least one output); a bfac that is not 16-byte aligned
+ * QPB_ERR_INVALID_ARG; a missing device last.
+ * Follow-ups: the unfactored qpb_solve_backward_dual with T directions (its u
+ * comes out of the set-up sweep and needs another construction), the n <= 128
+ * Gram class, qpb.diff (torch's batched gradients need a vmap rule), and the
+ * version bump to 0.15.
+ * Device pointers; asynchronous on `stream`. */
+#define QPB_SHARED_RHS 4 /* gx and glam are ONE set of T right-hand sides for the whole batch */
+#define QPB_MAX_RHS 256  /* >= n + m at the largest shape: every column of K^-1 in one call */
+
+int qpb_solve_factored_backward_multi(const qpb_desc *desc, const double *bfac,
+				      const uint32_t *active,
+				      const int32_t *status, int32_t nrhs,
+				      int32_t shared, const double *gx,
+				      const double *glam, double *gf,
+				      double *gb, void *stream);
+
+/* Same with host pointers (bfac included: the call uploads it). */
+int qpb_solve_factored_backward_multi_host(const qpb_desc *desc,
+					   const double *bfac,
+					   const uint32_t *active,
+					   const int32_t *status,
+					   int32_t nrhs, int32_t shared,
+					   const double *gx,
+					   const double *glam, double *gf,
+					   double *gb);
+
+int qpb_solve_box_backward_multi(const qpb_desc *desc, int32_t shared,
+				 const double *H, const uint32_t *active,
+				 const int32_t *status, int32_t nrhs,
+				 const double *gx, const double *glam,
+				 double *gf, double *glb, double *gub,
+				 void *stream);
+
+/* Same with host pointers (with QPB_SHARED_H, H is one matrix). */
+int qpb_solve_box_backward_multi_host(const qpb_desc *desc, int32_t shared,
+				      const double *H, const uint32_t *active,
+				      const int32_t *status, int32_t nrhs,
+				      const double *gx, const double *glam,
+				      double *gf, double *glb, double *gub);
 
 /* Reference-semantics solvers (qp_solvers.c replicas). */
 typedef enum qpb_ref_mode {
