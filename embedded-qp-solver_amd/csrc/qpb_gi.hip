@@ -123,6 +123,18 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 //      is the lower one negates the lane's row of D -- the negated row of A would
 //      have swept into exactly that -- before s is formed.  The loop and the
 //      outputs are the range form's.
+#ifdef QPB_WAVE_TRACE
+// diagnostic build only (tools/wave_timeline.py): the low 32 bits of the
+// 100 MHz real-time counter into 32-bit word w (12 .. 15: the record's free
+// words 6 and 7) of the group's 8-word record
+__device__ __forceinline__ void wave_stamp32(unsigned long long *dbg, long long grp, int w) {
+  if (!dbg) return;
+  unsigned long long t;
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  if (threadIdx.x == 0) reinterpret_cast<uint32_t *>(dbg)[16ull * grp + w] = (uint32_t)t;
+}
+#endif
+
 template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false, int FM = 0>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
@@ -898,6 +910,9 @@ __device__ __forceinline__ void gi_group(
     wave_lds_sync();
   }
   clk.tick(10);
+#ifdef QPB_WAVE_TRACE
+  if (!STAMP) wave_stamp32(dbg, grp, 12);  // the loop has ended
+#endif
   // EQ: from here on the multiplier of the caller's row (a flipped equality's is -um)
   // RG: the clamp first, on the multiplier of the side held; then the sign of
   // a lower-side position, so that H x + f + A^T lam = 0 with the caller's A
@@ -955,8 +970,7 @@ __device__ __forceinline__ void gi_group(
       });
     }
   });
-  double *lamb = Tv;  // lambda scatter (32) over the dead R; the solves below capture in Tv[32:48]
-  double *xcap = Tv + 2 * NL;
+  double *lamb = Tv;  // lambda scatter (32) over the dead R
 #pragma unroll
   for (int r = 0; r < 2; ++r) lamb[l + NL * r] = 0.0;
   wave_lds_sync();
@@ -994,6 +1008,24 @@ __device__ __forceinline__ void gi_group(
   }
   // x = -H^{-1} (f + A^T lam): g = f + sum_k u_k a_{iam_k}, then the two solves
   double gl = fl;
+#ifdef QPB_WAVE_TRACE
+  if (!STAMP) {
+    // before and after the wait for the gathered rows: the empty asm reads
+    // every row asked for, so the compiler's own wait stands in front of it
+    wave_stamp32(dbg, grp, 13);
+    unroll<2>([&](auto H) {
+      constexpr int k0 = 8 * H;
+      if (k0 < qm) {
+        unroll<8>([&](auto K) {
+          constexpr int kk = k0 + K;
+          const double arrived = arow[kk];
+          asm volatile("" ::"v"(arrived));
+        });
+      }
+    });
+    wave_stamp32(dbg, grp, 14);  // the gather has arrived
+  }
+#endif
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
     if (k0 < qm) {
@@ -1003,7 +1035,13 @@ __device__ __forceinline__ void gi_group(
       });
     }
   });
-  const double xl = solve_x(gl, invd, Lrow, Lp, l, xcap);
+  const double xl = solve_x_frozen(gl, invd, Lrow, Lp, l);
+#ifdef QPB_WAVE_TRACE
+  if (!STAMP) {
+    asm volatile("" ::"v"(xl));
+    wave_stamp32(dbg, grp, 15);  // x is solved
+  }
+#endif
   status = x_status(status, xl);
   if (live_o && (N16 || l < n)) at_off<double>(xg + go0 * n, (slo * (uint32_t)n + (uint32_t)l) * 8u) = xl;
   if (live_o && l == 0) {

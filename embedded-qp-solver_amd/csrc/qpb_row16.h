@@ -121,6 +121,8 @@ __device__ __forceinline__ double take_diagonal(double *R, int l, int q) {
 // compiler schedules: no hazard contract); finished lanes keep updating (dead
 // values) and the components are captured by same-address LDS stores in
 // xcap (16).  Lrow: row l of L (entries past l are dead), invd = 1 / L[l][l].
+// Used by gi_box and kkt_bwd_box; gi_dense runs solve_x_frozen below, the same
+// arithmetic without the capture.
 __device__ __forceinline__ double solve_x(double gl, double invd, const double (&Lrow)[NL], const double *Lp, int l,
                                           double *xcap) {
   {
@@ -145,6 +147,46 @@ __device__ __forceinline__ double solve_x(double gl, double invd, const double (
   }
   wave_lds_sync();
   return -xcap[l];
+}
+
+// solve_x without the capture (gi_dense): a finished lane is frozen by EXEC
+// instead.  One step under the lanes l >= K (FWD) or l <= K of every row:
+// t = acc invd, acc -= t_K mul, the same product and the same fused
+// multiply-add on the same numbers as solve_x's step K (t_K read from lane K
+// by the FMA itself, two wait states after its product; the multiplier's sign
+// by the source modifier).  A lane leaves the mask after its own step, so its
+// t stays the finished component: no broadcast move, no LDS store.  All 64
+// lanes must be live on entry (the callers run one wavefront per workgroup
+// and call this outside divergent code; -DQPB_CHECK_EXEC traps where that does
+// not hold); EXEC is all ones again on exit, and
+// it changes only inside the one asm statement, where the compiler places
+// nothing.
+template <int K, bool FWD>
+__device__ __forceinline__ void frozen_step(double &acc, double &t, double invd, double mul) {
+  constexpr unsigned m16 = FWD ? (0xFFFFu << K) & 0xFFFFu : 0xFFFFu >> (NL - 1 - K);
+  asm volatile("s_mov_b32 exec_lo, %4\n\ts_mov_b32 exec_hi, %4\n\t"
+               "v_mul_f64 %1, %0, %2\n\ts_nop 1\n\t"
+               "v_fmac_f64_dpp %0, %1, -%3 row_newbcast:%5 row_mask:0xf bank_mask:0xf\n\t"
+               "s_mov_b64 exec, -1"
+               : "+v"(acc), "+v"(t)
+               : "v"(invd), "v"(mul), "i"(m16 * 0x10001u), "i"(K));
+}
+// x_l as solve_x returns it, bit for bit: L y = g forward, then L^T x = -y
+// backward from the y each lane kept
+__device__ __forceinline__ double solve_x_frozen(double gl, double invd, const double (&Lrow)[NL], const double *Lp,
+                                                 int l) {
+#ifdef QPB_CHECK_EXEC
+  // diagnostic build: the precondition of frozen_step, all 64 lanes live
+  if (__builtin_amdgcn_read_exec() != ~0ull) __builtin_trap();
+#endif
+  double acc = gl, y = 0.0, x = 0.0;
+  unroll<NL>([&](auto K) { frozen_step<K, true>(acc, y, invd, Lrow[K]); });
+  acc = y;
+  unroll<NL>([&](auto K) {
+    constexpr int kk = NL - 1 - K;
+    frozen_step<kk, false>(acc, x, invd, Lp[lrow(kk) + l]);
+  });
+  return -x;
 }
 
 // a non-finite x on any lane -> QPB_NUMERICAL for a QP that was QPB_OK

@@ -16,6 +16,13 @@ shader clock, and its hardware location (HW_ID, XCC_ID).  From those:
   - the time a SIMD holds fewer than 3 waves while more waves are still to
     start (replacement gaps), and the gap from a wave's end to the start of
     the wave that takes its slot;
+  - the end of a wave's life, from four more stamps (the low 32 bits of the
+    real-time counter in the record's words 6 and 7): the loop's exit, the
+    moment before the wait for the gathered rows of A, their arrival, and x
+    solved.  Per wave, as mean / p50 / p90: pre_gather_us (loop exit to the
+    wait: the gather's issue and the work that does not need it),
+    gather_wait_us (the wait itself), x_solve_us (arrival to x: the sum over
+    the rows and row16::solve_x) and end_of_life_us (loop exit to the end);
   - the shader clock each wave ran at, Δs_memtime / Δs_memrealtime x 100 MHz
     (MI355X_MICROARCH.md "DVFS give-back" item 6), unprofiled.
 """
@@ -152,6 +159,27 @@ def concurrency(key):
             {str(v): int(n) for v, n in zip(*np.unique(mx, return_counts=True))})
 
 
+
+
+def dist(v):
+    return {"mean": float(v.mean()), "p50": float(np.median(v)), "p90": float(np.percentile(v, 90))}
+
+
+def lo32_us(a, b):
+    """b - a in us, both the low 32 bits of the 100 MHz counter"""
+    return ((b.astype(np.int64) - a.astype(np.int64)) & 0xFFFFFFFF) * 0.01
+
+
+m32 = np.uint64(0xFFFFFFFF)
+t_exit, t_pre = r[:, 6] & m32, r[:, 6] >> np.uint64(32)
+t_arr, t_x = r[:, 7] & m32, r[:, 7] >> np.uint64(32)
+end_of_life = None
+if (r[:, 6] != 0).all() and (r[:, 7] != 0).all():  # a build with the end-of-life stamps
+    end_of_life = {"pre_gather_us": dist(lo32_us(t_exit, t_pre)), "gather_wait_us": dist(lo32_us(t_pre, t_arr)),
+                   "x_solve_us": dist(lo32_us(t_arr, t_x)), "store_and_end_us": dist(lo32_us(t_x, r[:, 1] & m32)),
+                   "end_of_life_us": dist(lo32_us(t_exit, r[:, 1] & m32)),
+                   "loop_us": dist(lo32_us(r[:, 5] & m32, t_exit))}
+
 cu_share, cu_max = concurrency(simd_key >> 2)
 simd_share, simd_max = concurrency(simd_key)
 tot = nsimd * span
@@ -174,6 +202,7 @@ out = {
                          "p99": float(np.percentile(life, 99)), "max": float(life.max())},
     "input_wait_us": {"mean": float(((rtl - rt0) * 0.01).mean()), "p50": float(np.median((rtl - rt0) * 0.01)),
                       "p90": float(np.percentile((rtl - rt0) * 0.01, 90))},
+    "end_of_life": end_of_life,
     "end_after_store_drain": "wtrace2" in qpb.LIB_PATH,
     "slot_fill": float(resident),
     "time_share_by_resident_waves": {str(k): round(v / tot, 4) for k, v in fill.items()},
@@ -203,6 +232,7 @@ for lo, hi in zip(s, e):
     occ[i0:i1 + 1] += 1  # coarse: counts a wave in every bin it touches
 out["resident_waves_per_10us_bin"] = occ.astype(int).tolist()
 od = os.path.join(ROOT, "gpurun_out", "wtrace")
+od = os.environ.get("WTRACE_OUT", od)  # another directory for the JSON
 os.makedirs(od, exist_ok=True)
 tag = "_drain" if "wtrace2" in qpb.LIB_PATH else ""
 with open(os.path.join(od, f"wave_timeline_{fam}_{B}{tag}.json"), "w") as fh:
