@@ -5,9 +5,10 @@ import os, sys, numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle'))
 import oracle
 
-def gi(H, f, A, b, rule, tol=1e-10, trace=None):
+def gi(H, f, A, b, rule, tol=1e-10, trace=None, max_it=300):
     # trace: a list that receives (q, 'add' | 'drop', k) per iteration when given
     # (k: the active position a drop removes, -1 for an add)
+    # max_it: the cap on the trips (ADD + DROP); the library's default is 4 (n + m) + 8
     n = len(f); m = len(b)
     L = np.linalg.cholesky(H)
     D0 = np.linalg.solve(L, A.T).T          # A L^{-T}
@@ -18,7 +19,7 @@ def gi(H, f, A, b, rule, tol=1e-10, trace=None):
     Dc = D0.copy()
     it = adds = drops = 0
     thr = -tol * (1 + np.abs(b) / an)        # on s/|a|
-    while it < 300:
+    while it < max_it:
         q = len(W)
         act = np.zeros(m, bool); act[W] = True
         viol = (~act) & (s / an < thr)
