@@ -37,8 +37,9 @@
 //           parallel triangular solves with L kept in LDS.
 //
 // Data layout per QP (lane l = 0..15 of the QP's 16-lane DPP row):
-//   registers  rows l + 16 r (r < MR) of D, their slacks, 1/||a_row||,
-//              |D row|^2, |free part|^2, active flags; multiplier / row of
+//   registers  rows l + 16 r (r < MR) of D, their slacks, their violation
+//              thresholds (the high word is a NaN's while the row is active,
+//              with a copy to put back), |D row|^2, |free part|^2; multiplier / row of
 //              active position l, R[l][l] and its reciprocal; in a DROP the
 //              parameters of Givens rotation l
 //   LDS        L (packed rows), R (16 x 16 column-major, zero diagonal; its
@@ -74,6 +75,19 @@ __device__ __forceinline__ void bdot_rows(double vec, const double (&x)[MR][NL],
 #pragma unroll
   for (int r = 0; r < MR; ++r) out[r] = a[r][0] + a[r][1];
 }
+
+// The high word of a double, and the double with that word replaced (the low
+// word kept): sub-register moves, no arithmetic
+__device__ __forceinline__ uint32_t hi32(double v) {
+  return (uint32_t)(__builtin_bit_cast(unsigned long long, v) >> 32);
+}
+__device__ __forceinline__ double with_hi32(double v, uint32_t hi) {
+  const unsigned long long lo = __builtin_bit_cast(unsigned long long, v) & 0xFFFFFFFFull;
+  return __builtin_bit_cast(double, lo | ((unsigned long long)hi << 32));
+}
+// The high word a row's threshold carries while the row is in the active set:
+// a quiet NaN, so the selection's s < thr is false for it
+constexpr uint32_t kActiveHi = 0x7FF80000u;
 
 // MR: rows of D per lane (m <= 16 MR).  N16: n == 16 (coalesced loads).
 // FULL: n == 16 and m == 16 MR (no padding rows: no masking anywhere).
@@ -195,7 +209,9 @@ __device__ __forceinline__ void gi_group(
   double s[MR], bl[MR], thr[MR];
   float ddr[MR];  // |D[r,:]|^2 (the dependency test's scale; clamped to FLT_MAX)
   float fn2[MR];  // |D[r, q:]|^2, the free part of the row (scale of the selection key)
-  bool act[MR];
+  // The active flag of a row lives in thr: the high word is kActiveHi while the
+  // row is in the active set, and thh keeps the word to put back at a DROP
+  uint32_t thh[MR];
   bool infeasible_row = false;
   // b and f with the matrices (same round trip)
   double bv[MR];
@@ -283,7 +299,6 @@ __device__ __forceinline__ void gi_group(
                          (eqr && has_hi && hi > feas_tol * (1.0 + __builtin_fabs(hi))))) ||
                        (ok && !eqr && rg.w[r] < -feas_tol * (nrm + beta));
       thr[r] = (eqr && !has_hi) ? __builtin_nan("") : thr[r];
-      act[r] = false;
       return;
     }
     bl[r] = ok ? (bv[r] == bv[r] ? bv[r] : kInf) : 0.0;
@@ -298,7 +313,6 @@ __device__ __forceinline__ void gi_group(
       infeasible_row = infeasible_row || (eqr && nrm2 == 0.0 && bl[r] > feas_tol * (1.0 + __builtin_fabs(bl[r])));
       thr[r] = (eqr && !(__builtin_fabs(bv[r]) < kInf)) ? __builtin_nan("") : thr[r];
     }
-    act[r] = false;
   };
   [[maybe_unused]] double fdn[MR];    // FM == 2: |D[r,:]|^2 from the buffer
   [[maybe_unused]] bool fspd = true;  // FM == 2: the buffer's H was positive definite
@@ -557,6 +571,10 @@ __device__ __forceinline__ void gi_group(
     bool nan_row = false;
 #pragma unroll
     for (int r = 0; r < MR; ++r) nan_row = nan_row || thr[r] != thr[r];
+    // (a NaN here is an input's; a QP that has one never enters the loop, where
+    // a NaN high word comes to mean "active")
+#pragma unroll
+    for (int r = 0; r < MR; ++r) thh[r] = hi32(thr[r]);
     const double bad = row_min(nan_row ? -2.0 : infeasible_row ? -1.0 : 0.0);
     const bool inf0 = bad < 0.0;
     status = !spd ? QPB_NOT_SPD : (bad < -1.5 ? QPB_NUMERICAL : inf0 ? QPB_INFEASIBLE : QPB_MAX_ITER);
@@ -599,13 +617,13 @@ __device__ __forceinline__ void gi_group(
           // (w - s; NaN or +inf where the row has no other side), same key
           const double so = rg.w[r] - s[r];
           const double sv = so < s[r] ? so : s[r];
-          const bool viol = !act[r] && sv < thr[r];
+          const bool viol = sv < thr[r];  // false for an active row (thr NaN)
           const float kf = __builtin_fmaf((float)(-sv), __builtin_amdgcn_rsqf(fn2[r]), 0x1p-100f);
           const uint32_t kr = (__float_as_uint(kf) & ~31u) | (uint32_t)(l + NL * r);
           key = viol && kr > key && l + NL * r >= meq ? kr : key;
           continue;
         }
-        const bool viol = !act[r] && s[r] < thr[r];
+        const bool viol = s[r] < thr[r];  // false for an active row (thr NaN)
         // fn2 in [0, FLT_MAX] (clamped where it shrinks); the 2^-100 floor keeps
         // a violated row's key above 31 -- never 0, the "none violated" key --
         // when the ratio underflows (row 0 included)
@@ -818,7 +836,7 @@ __device__ __forceinline__ void gi_group(
         else if constexpr (EQ) eqs.pneg = eqs.sel && eqs.flip;
       }
 #pragma unroll
-      for (int r = 0; r < MR; ++r) act[r] = act[r] || (l == owner && r == prow);
+      for (int r = 0; r < MR; ++r) thr[r] = with_hi32(thr[r], (l == owner && r == prow) ? kActiveHi : hi32(thr[r]));
       if constexpr (EQ) eqs.q += eqs.sel ? 1 : 0;
       ++q;
       selecting = true;
@@ -829,7 +847,8 @@ __device__ __forceinline__ void gi_group(
       const int k = (int)row_min_u32(attains ? (uint32_t)l : 31u) & (NL - 1);
       const int c = __shfl(iam, k, NL);
 #pragma unroll
-      for (int r = 0; r < MR; ++r) act[r] = act[r] && !(l == (c & (NL - 1)) && r == (c >> 4));
+      for (int r = 0; r < MR; ++r)
+        thr[r] = with_hi32(thr[r], (l == (c & (NL - 1)) && r == (c >> 4)) ? thh[r] : hi32(thr[r]));
       const double un = __shfl(um, (l + 1) & (NL - 1), NL);
       const int in = __shfl(iam, (l + 1) & (NL - 1), NL);
       if (l >= k && l < q - 1) {
@@ -990,10 +1009,13 @@ __device__ __forceinline__ void gi_group(
     if (live_o && (FULL || row < m))
       at_off<double>(lamg + go0 * m, (slo * (uint32_t)m + (uint32_t)row) * 8u) = lamr[r];
   }
+  // row r of the lane is in the active set: its threshold carries the NaN word.
+  // A QP that ran no trip has no active row -- it may hold an input's NaN.
+  auto in_set = [&](int r) { return it != 0 && thr[r] != thr[r]; };
   uint32_t w0 = 0;
 #pragma unroll
   for (int r = 0; r < MR; ++r) {
-    const unsigned long long bal = __ballot(act[r]);
+    const unsigned long long bal = __ballot(in_set(r));
     w0 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
   }
   if (live_o && l == 0 && m > 0) at_off<uint32_t>(actg + go0, slo * 4u) = w0;
@@ -1001,7 +1023,7 @@ __device__ __forceinline__ void gi_group(
     uint32_t w1 = 0;
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
-      const unsigned long long bal = __ballot(act[r] && rg.low[r] && l + NL * r >= meq);
+      const unsigned long long bal = __ballot(in_set(r) && rg.low[r] && l + NL * r >= meq);
       w1 |= (uint32_t)((bal >> sh) & 0xFFFFull) << (16 * r);
     }
     if (lowg && live_o && l == 0 && m > 0) at_off<uint32_t>(lowg + go0, slo * 4u) = w1;
