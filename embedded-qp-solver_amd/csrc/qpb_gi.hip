@@ -119,6 +119,14 @@ constexpr uint32_t kActiveHi = 0x7FF80000u;
 // active at their lower bound.  The norms (thr, ddr, fn2) do not depend on
 // the side.  A dropped row keeps its side; its slack follows the updates like
 // any inactive row's, and it can come back on either side.
+// BX (qpb_solve_range_box, on RG): the last n of the m rows are the variables'
+// bounds, row mg + j being lb_j <= x_j <= ub_j (ubg, lbg: n per QP, either may
+// be NULL); bg, blg and Ag hold the mg rows before them only.  A lane's row
+// l + 16 r sits where the materialised [G; I] would put it; a row >= mg is
+// e_{row - mg} made in registers -- no address of G is formed for it in any of
+// the three load paths -- row_norms runs on it unchanged, so the thresholds are
+// the materialised form's bits, and in the x recovery its position adds
+// um e_j.  Everything between is the RG form's code.
 // FM (qpb_factor_shared and qpb_solve_factored; qpb_factor.h has the buffer):
 //   1  the factor kernel's body: ONE problem (batch 1, no f and no b), this
 //      form's own load and sweep, then L, D, the rows' norms, A and what the
@@ -149,7 +157,8 @@ __device__ __forceinline__ void wave_stamp32(unsigned long long *dbg, long long 
 }
 #endif
 
-template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false, int FM = 0>
+template <int MR, bool N16, bool FULL, bool STAMP, bool EQ = false, bool SH = false, bool RG = false, int FM = 0,
+          bool BX = false>
 __device__ __forceinline__ void gi_group(
     double *lds, const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Ag,
     const double *__restrict__ bg, double *__restrict__ xg, double *__restrict__ lamg,
@@ -157,8 +166,10 @@ __device__ __forceinline__ void gi_group(
     long long batch, int max_iter, double feas_tol, int flags, unsigned long long *__restrict__ dbg,
     long long grp, [[maybe_unused]] int meq = 0, [[maybe_unused]] long long strideH = 0,
     [[maybe_unused]] long long strideA = 0, [[maybe_unused]] const double *__restrict__ blg = nullptr,
-    [[maybe_unused]] uint32_t *__restrict__ lowg = nullptr) {
+    [[maybe_unused]] uint32_t *__restrict__ lowg = nullptr, [[maybe_unused]] int mg = 0,
+    [[maybe_unused]] const double *__restrict__ ubg = nullptr, [[maybe_unused]] const double *__restrict__ lbg = nullptr) {
   static_assert(!FULL || N16, "FULL implies n == 16");
+  static_assert(!BX || (RG && FM == 0), "the box rows are the unfactored range form's");
   static_assert(!RG || (EQ && SH), "the range form is built on the EQ and the shared forms");
   static_assert(!SH || !STAMP, "the shared form has no stamped build");
   static_assert(FM == 0 || (!STAMP && (FM == 1 ? !EQ && !SH && !RG : SH)),
@@ -182,6 +193,7 @@ __device__ __forceinline__ void gi_group(
   if constexpr (FULL) {
     n = NL;
     m = NL * MR;
+    if constexpr (BX) mg = NL * (MR - 1);
   }
 
   double *base = slot_base(lds, slot);
@@ -201,7 +213,8 @@ __device__ __forceinline__ void gi_group(
   const long long gi0 = (flags & QPB_FLAG_DIAG_L2) ? (g0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (g0 & 16383) : g0;
   const double *Hs = SH ? Hg + gi0 * strideH : Hg + gi0 * (long long)n * n;
   // m == 0: A/b may be NULL -- point the (masked) row loads at H instead
-  const double *As = m > 0 ? (SH ? Ag + gi0 * strideA : Ag + gi0 * (long long)m * n) : Hs;
+  // (BX: the same for mg == 0, and no load goes through As then)
+  const double *As = (BX ? mg : m) > 0 ? (SH ? Ag + gi0 * strideA : Ag + gi0 * (long long)m * n) : Hs;
   const double *bs = m > 0 ? bg + gi0 * (long long)m : Hs;
   const uint32_t un = (uint32_t)n, umn = (uint32_t)m * un;
   double Lr[NL];  // row l of H, becomes row l of L
@@ -221,6 +234,34 @@ __device__ __forceinline__ void gi_group(
   if constexpr (FM == 1) {
 #pragma unroll
     for (int r = 0; r < MR; ++r) bv[r] = 0.0;
+  } else if constexpr (BX) {
+    // rows < mg: bu and bl at the row, mg per QP; rows mg + j: ub and lb at j, n
+    // per QP.  Each of the four NULL (wave-uniform) when nothing has that side;
+    // a lane whose rows are not of an array's kind reads its element 0
+    const double *hi_r = bg && mg > 0 ? bg + gi0 * (long long)mg : nullptr;
+    const double *lo_r = blg && mg > 0 ? blg + gi0 * (long long)mg : nullptr;
+    const double *hi_b = ubg ? ubg + gi0 * n : nullptr, *lo_b = lbg ? lbg + gi0 * n : nullptr;
+    unroll<MR>([&](auto R) {
+      constexpr int r = R;
+      const int row = l + NL * r;
+      if constexpr (FULL && r < MR - 1) {  // general rows only
+        const uint32_t off = (sl * (uint32_t)mg + (uint32_t)row) * 8u;
+        bv[r] = hi_r ? at_off<double>(hi_r, off) : kInf;
+        rg.lo[r] = lo_r ? at_off<double>(lo_r, off) : -kInf;
+      } else if constexpr (FULL) {  // the variables' rows only
+        const uint32_t off = (sl * un + (uint32_t)l) * 8u;
+        bv[r] = hi_b ? at_off<double>(hi_b, off) : kInf;
+        rg.lo[r] = lo_b ? at_off<double>(lo_b, off) : -kInf;
+      } else {
+        const bool gen = row < mg;
+        const uint32_t offr = (sl * (uint32_t)mg + (uint32_t)(gen ? row : 0)) * 8u;
+        const uint32_t offb = (sl * un + (uint32_t)((!gen && row < m) ? row - mg : 0)) * 8u;
+        const double ur = hi_r ? at_off<double>(hi_r, offr) : kInf, ub = hi_b ? at_off<double>(hi_b, offb) : kInf;
+        const double lr = lo_r ? at_off<double>(lo_r, offr) : -kInf, lb = lo_b ? at_off<double>(lo_b, offb) : -kInf;
+        bv[r] = gen ? ur : ub;
+        rg.lo[r] = gen ? lr : lb;
+      }
+    });
   } else if constexpr (RG) {
     // bu and bl, each NULL (wave-uniform) when no row has that side
     const double *lo_s = blg ? blg + gi0 * (long long)m : nullptr;
@@ -361,7 +402,16 @@ __device__ __forceinline__ void gi_group(
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const int row = NL * r + 2 * t + hr;
-        if constexpr (FULL)
+        if constexpr (BX) {
+          // rows >= mg are synthesised: the lane's two columns hc, hc + 1 of
+          // e_{row - mg} take the place of the loaded pair (zeros past m)
+          const int jb = row < m ? row - mg : -2;
+          const double2 e = make_double2(jb == hc ? 1.0 : 0.0, jb == hc + 1 ? 1.0 : 0.0);
+          if constexpr (FULL)
+            v[t] = r < MR - 1 ? *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]) : e;
+          else
+            v[t] = row < mg ? *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]) : e;
+        } else if constexpr (FULL)
           v[t] = *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]);
         else
           v[t] = row < m ? *reinterpret_cast<const double2 *>(&Al[(NL * r + 2 * t) * NL]) : make_double2(0.0, 0.0);
@@ -411,10 +461,15 @@ __device__ __forceinline__ void gi_group(
       const int rc = ok ? row : 0;
       const uint32_t arow_off =
           SH ? sl * (uint32_t)strideA * 8u + (uint32_t)rc * un * 8u : (sl * umn + (uint32_t)rc * un) * 8u;
+      if (BX && row >= mg) {  // e_{row - mg} (zeros past m): nothing is read
 #pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const double a = at_off<double>(As, arow_off + (uint32_t)(j < n ? j : n - 1) * 8u);
-        E[r][j] = (ok && j < n) ? a : 0.0;
+        for (int j = 0; j < NL; ++j) E[r][j] = (ok && row - mg == j) ? 1.0 : 0.0;
+      } else {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double a = at_off<double>(As, arow_off + (uint32_t)(j < n ? j : n - 1) * 8u);
+          E[r][j] = (ok && j < n) ? a : 0.0;
+        }
       }
       row_norms(r, E[r]);
     }
@@ -961,7 +1016,7 @@ __device__ __forceinline__ void gi_group(
   const uint32_t slo = (uint32_t)(live_o ? slot_o : rem_o - 1);
   const long long gio0 =
       (flags & QPB_FLAG_DIAG_L2) ? (go0 & 511) : (flags & QPB_FLAG_DIAG_MALL) ? (go0 & 16383) : go0;
-  const double *Aso = SH ? (m > 0 ? Ag + gio0 * strideA : Hg + gio0 * strideH)
+  const double *Aso = SH ? ((BX ? mg : m) > 0 ? Ag + gio0 * strideA : Hg + gio0 * strideH)
                          : (m > 0 ? Ag + gio0 * (long long)m * n : Hg + gio0 * (long long)n * n);
   // The A-row loads go out first, in at most two groups of eight (one
   // wave-uniform test per group: a test per load made each load a branch
@@ -973,15 +1028,25 @@ __device__ __forceinline__ void gi_group(
   // each load adds the broadcast offset to this lane's 32-bit column offset
   // inside the group's A block -- a DPP move and one 32-bit add per load on the
   // group's scalar base.
-  const uint32_t iob = (uint32_t)(iam > 0 ? iam : 0) * (uint32_t)n * 8u;
+  // BX: a position whose row is mg + j holds a variable's bound and adds
+  // um e_j: jbx is j there and -1 elsewhere, nothing of G is needed for it (its
+  // load goes to row 0, the line the others' loads have brought in, and its
+  // value is not used), and with mg == 0 no load goes out at all
+  const uint32_t iob = (uint32_t)((iam > 0 && (!BX || iam < mg)) ? iam : 0) * (uint32_t)n * 8u;
   asm volatile("s_nop 1" ::"v"(iob));  // its DPP reads below may sit behind a branch only
+  [[maybe_unused]] const int jbx = (BX && iam >= mg) ? iam - mg : -1;
+  if constexpr (BX) asm volatile("s_nop 1" ::"v"(jbx));
   const int lc = l < n ? l : n - 1;
   const uint32_t acol = SH ? slo * ((uint32_t)strideA * 8u) + (uint32_t)lc * 8u
                            : (slo * (uint32_t)m * (uint32_t)n + (uint32_t)lc) * 8u;
   double arow[NL];
+  if constexpr (BX) {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) arow[k] = 0.0;
+  }
   unroll<2>([&](auto H) {
     constexpr int k0 = 8 * H;
-    if (k0 < qm) {
+    if (k0 < qm && (!BX || mg > 0)) {
       __builtin_amdgcn_sched_barrier(0);
       unroll<8>([&](auto K) {
         constexpr int kk = k0 + K;
@@ -1053,7 +1118,14 @@ __device__ __forceinline__ void gi_group(
     if (k0 < qm) {
       unroll<8>([&](auto K) {
         constexpr int kk = k0 + K;
-        if (kk < qm) gl = __builtin_fma(bc<kk>(um), (N16 || l < n) ? arow[kk] : 0.0, gl);
+        if constexpr (BX) {
+          // the fused multiply-add the materialised form does on the unit row's entry
+          const int jb = bci<kk>(jbx);
+          const double a = jb < 0 ? ((N16 || l < n) ? arow[kk] : 0.0) : (l == jb ? 1.0 : 0.0);
+          if (kk < qm) gl = __builtin_fma(bc<kk>(um), a, gl);
+        } else {
+          if (kk < qm) gl = __builtin_fma(bc<kk>(um), (N16 || l < n) ? arow[kk] : 0.0, gl);
+        }
       });
     }
   });
@@ -1151,6 +1223,22 @@ __global__ __launch_bounds__(64, OCC) void gi_dense_range_kernel(
   gi_group<MR, N16, FULL, false, true, true, true>(lds, Hg, fg, Ag, bug, xg, lamg, actg, statg, itg, n, m, batch,
                                                    max_iter, feas_tol, 0, nullptr, blockIdx.x, meq, strideH, strideA,
                                                    blg, lowg);
+}
+
+// qpb_solve_range_box's form: the range form with BX.  `m` counts all rows,
+// mg + n; rows mg .. m-1 are the variables' bounds lbg <= x <= ubg (n per QP,
+// either may be NULL), whose rows of A -- the identity -- are synthesised
+template <int MR, bool N16, bool FULL, int OCC>
+__global__ __launch_bounds__(64, OCC) void gi_dense_range_box_kernel(
+    const double *__restrict__ Hg, const double *__restrict__ fg, const double *__restrict__ Gg,
+    const double *__restrict__ blg, const double *__restrict__ bug, const double *__restrict__ lbg,
+    const double *__restrict__ ubg, double *__restrict__ xg, double *__restrict__ lamg, uint32_t *__restrict__ actg,
+    uint32_t *__restrict__ lowg, int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, int mg, int meq,
+    long long batch, int max_iter, double feas_tol, long long strideH, long long strideA) {
+  __shared__ double lds[QPB * SLOT];
+  gi_group<MR, N16, FULL, false, true, true, true, 0, true>(lds, Hg, fg, Gg, bug, xg, lamg, actg, statg, itg, n, m,
+                                                            batch, max_iter, feas_tol, 0, nullptr, blockIdx.x, meq,
+                                                            strideH, strideA, blg, lowg, mg, ubg, lbg);
 }
 
 // qpb_factor_shared's kernel: one workgroup, whose first row factors the one
@@ -1279,6 +1367,23 @@ extern "C" hipError_t qpb_launch_gi_range(const qpb_desc *d, int meq, long long 
     hipLaunchKernelGGL((qpb::gi_dense_range_kernel<MR(), N16(), FULL(), qpb::kEqOcc>), dim3((unsigned)blocks),
                        dim3(64), 0, stream, H, f, A, bl, bu, x, lam, active, lower, status, iters, d->n, d->m, meq,
                        (long long)d->batch, max_iter, tol, strideH, strideA);
+  });
+  return hipGetLastError();
+}
+
+// qpb_solve_range_box, n <= 16 and d->m = mg + n <= 32: the six forms by all the
+// rows, the last n of them the variables' bounds (mg >= 0; G unread at mg == 0)
+extern "C" hipError_t qpb_launch_gi_range_box(const qpb_desc *d, int mg, int meq, long long strideH, long long strideA,
+                                              const double *H, const double *f, const double *G, const double *bl,
+                                              const double *bu, const double *lb, const double *ub, double *x,
+                                              double *lam, uint32_t *active, uint32_t *lower, int32_t *status,
+                                              int32_t *iters, hipStream_t stream) {
+  const long long blocks = (d->batch + qpb::QPB - 1) / qpb::QPB;
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto FULL) {
+    hipLaunchKernelGGL((qpb::gi_dense_range_box_kernel<MR(), N16(), FULL(), qpb::kEqOcc>), dim3((unsigned)blocks),
+                       dim3(64), 0, stream, H, f, G, bl, bu, lb, ub, x, lam, active, lower, status, iters, d->n, d->m,
+                       mg, meq, (long long)d->batch, max_iter, tol, strideH, strideA);
   });
   return hipGetLastError();
 }

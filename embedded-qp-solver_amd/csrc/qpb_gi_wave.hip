@@ -144,6 +144,20 @@ struct RangeFactorIn {
   const double *bl;  // as RangeArgs
   uint32_t *lower;
 };
+// RangeBoxArgs (qpb_solve_range_box): the range form, RangeArgs' two pointers
+// included, whose last n of the m rows are the variables' bounds: row mg + j is
+// lb_j <= x_j <= ub_j.  `m` counts all rows, mg + n; Ag, bg and bl hold the mg
+// rows before them only.  Lane l holds row l as in the materialised [G; I]; a
+// row >= mg starts from e_{l - mg} made in registers (as BOX does) and is never
+// read from anywhere, the set-up runs on it unchanged -- the thresholds are the
+// materialised form's bits -- and in the x recovery its position adds um e_j.
+struct RangeBoxArgs {
+  const double *bl;  // mg per QP, or NULL
+  uint32_t *lower;   // ceil(m/32) words per QP, or NULL
+  const double *lb;  // n per QP, or NULL: no variable has a lower bound
+  const double *ub;  // n per QP, or NULL
+  int mg;            // the general rows, 0 <= mg = m - n
+};
 template <int OCC, bool STAMP = false, bool REDO = false, bool BOX = false, bool EQ = false, bool SH = false,
           class... RGA>
 __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
@@ -152,7 +166,8 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     int32_t *__restrict__ statg, int32_t *__restrict__ itg, int n, int m, long long batch, int max_iter,
     double feas_tol, unsigned long long *__restrict__ dbg = nullptr, RGA... rga) {
   constexpr bool RF = (std::is_same_v<RGA, RangeFactorIn> || ...);
-  constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...) || RF;
+  constexpr bool BX = (std::is_same_v<RGA, RangeBoxArgs> || ...);
+  constexpr bool RG = (std::is_same_v<RGA, RangeArgs> || ...) || RF || BX;
   constexpr bool FO = (std::is_same_v<RGA, FactorOut> || ...), FI = (std::is_same_v<RGA, FactorIn> || ...) || RF;
   static_assert(sizeof...(RGA) <= 1 && (sizeof...(RGA) == 0 || RG || FO || FI), "one trailing argument at most");
   static_assert(!(FO || FI) || (!(STAMP || REDO || SH) && (!FO || !EQ)),
@@ -169,6 +184,14 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const auto ra = [](auto a) { return a; }(rga...);
     blg = ra.bl;
     lowg = ra.lower;
+  }
+  [[maybe_unused]] const double *lbg = nullptr, *ubg = nullptr;
+  [[maybe_unused]] int mg = 0;
+  if constexpr (BX) {
+    const RangeBoxArgs ra = [](RangeBoxArgs a) { return a; }(rga...);
+    lbg = ra.lb;
+    ubg = ra.ub;
+    mg = ra.mg;
   }
   [[maybe_unused]] const double *facg = nullptr;  // FI: the buffer
   [[maybe_unused]] double *faco = nullptr;        // FO: the buffer, and where the finding goes
@@ -207,7 +230,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   // and the bounds stay per QP -- they are read through Ag and bg at g)
   const double *Aq = BOX      ? Hq
                      : FI     ? facg + fct::layout(n, m).A
-                     : m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n)
+                     : (BX ? mg : m) > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)(BX ? mg : m) * n : Ag + g * (long long)m * n)
                              : Hq;
   const double *bq = BOX ? Hq : m > 0 ? bg + g * (long long)m : Hq;
   const bool rowok = l < m;
@@ -232,6 +255,15 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     const double v = bnd ? bnd[g * n + bi] : (l < n ? kInf : -kInf);
     bv = l < n ? v : -v;
     if (!(bv == bv)) bv = kInf;  // NaN bound: absent
+  } else if constexpr (BX) {
+    // rows < mg: bu and bl at l, mg per QP; row mg + j: ub and lb at j, n per
+    // QP; each of the four NULL when nothing has that side
+    const bool gen = l < mg;
+    const int bi = gen ? l : rowok ? l - mg : 0;
+    const double *hp = gen ? bg : ubg, *lp = gen ? blg : lbg;
+    const long long b0 = g * (long long)(gen ? mg : n) + bi;
+    bv = hp ? hp[b0] : kInf;
+    rg.lo[0] = lp ? lp[b0] : -kInf;
   } else if constexpr (RG) {
     // bu and bl, each NULL when no row has that side
     bv = bg ? bq[rowok ? l : 0] : kInf;
@@ -292,7 +324,9 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
   }
   if constexpr (!FI) {
     constexpr int RST = NP + 2;  // staged row stride
-    const int nn = n * n, h0 = (m < NP ? m : NP) * n, h1 = m * n - h0;  // A rows 0-31 | 32-63
+    // (BX: the mg rows that are there; the others are not read, not even clamped)
+    const int ma = BX ? mg : m;
+    const int nn = n * n, h0 = (ma < NP ? ma : NP) * n, h1 = ma * n - h0;  // A rows 0-31 | 32-63
     double hv[16], av[2][16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -351,13 +385,18 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
       // filled (peak E + L + H's 32 staged values, not E + L + A)
       stage(av[0]);
       wave_lds_sync();
-      fetch_row(E, l & (NP - 1), l < NP && rowok);
+      fetch_row(E, l & (NP - 1), l < NP && l < ma);
       wave_lds_sync();
-      if (m > NP) {
+      if (ma > NP) {
         stage(av[1]);
         wave_lds_sync();
-        fetch_row(E, l & (NP - 1), l >= NP && rowok);
+        fetch_row(E, l & (NP - 1), l >= NP && l < ma);
         wave_lds_sync();
+      }
+      if constexpr (BX) {
+        // row mg + j: e_j
+#pragma unroll
+        for (int j = 0; j < NP; ++j) E[j] = (l - mg == j && rowok) ? 1.0 : E[j];
       }
     }
     stage(hv);
@@ -938,6 +977,7 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
     // every active row's element first (one memory round trip instead of q
     // dependent ones), 16 at a time (one trip for q <= 16, the usual case;
     // 8 at a time was 0.3-0.6 % slower), then the sum in position order
+    // (BX: a position whose row is mg + j has the row e_j: wave-uniform, nothing read)
     const int lc = l < n ? l : 0;
     const int ias = iam > 0 ? iam : 0;
     unroll<NP / 16>([&](auto Hh) {
@@ -947,7 +987,13 @@ __global__ __launch_bounds__(64, OCC) void gi_wave_kernel(
         __builtin_amdgcn_sched_barrier(0);
         unroll<16>([&](auto K) {
           constexpr int kk = k0 + K;
-          arow[K] = kk < q ? Aq[__builtin_amdgcn_readlane(ias, kk) * n + lc] : 0.0;
+          if constexpr (BX) {
+            const int ik = __builtin_amdgcn_readlane(ias, kk);
+            if (kk < q && ik < mg) arow[K] = Aq[ik * n + lc];
+            else arow[K] = (kk < q && l == ik - mg) ? 1.0 : 0.0;
+          } else {
+            arow[K] = kk < q ? Aq[__builtin_amdgcn_readlane(ias, kk) * n + lc] : 0.0;
+          }
         });
         unroll<16>([&](auto K) {
           constexpr int kk = k0 + K;
@@ -1140,6 +1186,23 @@ extern "C" hipError_t qpb_launch_gi_wave_range(const qpb_desc *d, int meq, long 
   hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, true, qpb::wv::RangeArgs>),
                      dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, A, bu, x, lam, active, status, iters, d->n,
                      mm, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::RangeArgs{bl, lower});
+  return hipGetLastError();
+}
+
+// qpb_solve_range_box for the n <= 32, d->m = mg + n <= 64 class: the range
+// launcher's arguments for the mg general rows, lb and ub for the variables'
+extern "C" hipError_t qpb_launch_gi_wave_range_box(const qpb_desc *d, int mg, int meq, long long strideH,
+                                                   long long strideA, const double *H, const double *f,
+                                                   const double *G, const double *bl, const double *bu,
+                                                   const double *lb, const double *ub, double *x, double *lam,
+                                                   uint32_t *active, uint32_t *lower, int32_t *status, int32_t *iters,
+                                                   hipStream_t stream) {
+  const auto [max_iter, tol] = qpb_resolve_limits(d);
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | (strideA == 0 ? QPB_SHARED_A : 0);
+  const int mm = d->m | (meq << qpb::wv::kEqShift) | (shared << qpb::wv::kShShift);
+  hipLaunchKernelGGL((qpb::wv::gi_wave_kernel<3, false, false, false, true, true, qpb::wv::RangeBoxArgs>),
+                     dim3((unsigned)d->batch), dim3(64), 0, stream, H, f, G, bu, x, lam, active, status, iters, d->n,
+                     mm, (long long)d->batch, max_iter, tol, nullptr, qpb::wv::RangeBoxArgs{bl, lower, lb, ub, mg});
   return hipGetLastError();
 }
 

@@ -87,6 +87,17 @@ typedef hipError_t qpb_gi_range_launcher(const qpb_desc *d, int meq, long long s
                                          int32_t *status, int32_t *iters, hipStream_t stream);
 QPB_LAUNCHER qpb_gi_range_launcher qpb_launch_gi_range,  // n <= 16, m <= 32 (qpb_gi.hip)
     qpb_launch_gi_wave_range;                            // n <= 32, m <= 64 (qpb_gi_wave.hip)
+// qpb_solve_range_box: the BX forms of the range forms.  d->m counts all rows,
+// mg + n: the mg general rows of G (mg >= 0; G, bl, bu: mg per QP, G unread at
+// mg == 0, strideA 0 or mg n), then the variables' bounds lb <= x <= ub (n per
+// QP) as rows mg .. d->m-1.  Any of bl, bu, lb, ub and lower may be NULL.
+typedef hipError_t qpb_gi_range_box_launcher(const qpb_desc *d, int mg, int meq, long long strideH, long long strideA,
+                                             const double *H, const double *f, const double *G, const double *bl,
+                                             const double *bu, const double *lb, const double *ub, double *x,
+                                             double *lam, uint32_t *active, uint32_t *lower, int32_t *status,
+                                             int32_t *iters, hipStream_t stream);
+QPB_LAUNCHER qpb_gi_range_box_launcher qpb_launch_gi_range_box,  // n <= 16, mg + n <= 32 (qpb_gi.hip)
+    qpb_launch_gi_wave_range_box;                                // n <= 32, mg + n <= 64 (qpb_gi_wave.hip)
 // qpb_factor_shared: ONE H (n x n) and ONE A (m x n, NULL at m == 0) into the
 // class's factor buffer (qpb_factor.h), one small launch; fstatus may be NULL
 typedef hipError_t qpb_gi_factor_launcher(int n, int m, const double *H, const double *A, double *fac,

@@ -404,6 +404,29 @@ static_assert(route_factored(16, 32).step == route_range(16, 32).step &&
               route_factored(1, 65).step == 0);
 static_assert(kFactoredMaxN == kRangeMaxN && kFactoredMaxM == kRangeMaxM);
 
+// qpb_solve_range_box, mg general rows beside the n variables' bounds: the range
+// route of the materialised problem's shape, m' = mg + n rows -- the BX forms of
+// the RG forms sit in its two classes, lane for lane -- and its limit: step 0
+// above it, and the call is unsupported.  mg == 0 is a shape of its own here
+// (qpb_solve_range hands m == 0 to qpb_solve).
+constexpr Route route_range_box(int n, int mg) { return route_range(n, mg + n); }
+constexpr int kRangeBoxMaxN = kRangeMaxN, kRangeBoxMaxRows = kRangeMaxM;  // n, and mg + n
+
+static_assert(route_range_box(16, 16).kernel == Kernel::gi_dense && route_range_box(16, 17).kernel == Kernel::gi_wave &&
+              route_range_box(12, 20).kernel == Kernel::gi_dense);
+static_assert(route_range_box(32, 32).kernel == Kernel::gi_wave && route_range_box(32, 32).step == 1LL << 25);
+static_assert(route_range_box(32, 33).step == 0 && route_range_box(33, 0).step == 0);
+static_assert(route_range_box(1, 0).kernel == Kernel::gi_dense && route_range_box(16, 0).kernel == Kernel::gi_dense &&
+              route_range_box(17, 0).kernel == Kernel::gi_wave && route_range_box(16, 16).step == 1LL << 27);
+static_assert(route_range_box(kRangeBoxMaxN, kRangeBoxMaxRows - kRangeBoxMaxN).step > 0 &&
+              route_range_box(kRangeBoxMaxN + 1, 0).step == 0 && route_range_box(1, kRangeBoxMaxRows).step == 0);
+// its bits are qpb_solve_range's on [G; I]: that call's class and step at every corner
+static_assert(route_range_box(16, 16).kernel == route_range(16, 32).kernel &&
+              route_range_box(16, 16).step == route_range(16, 32).step &&
+              route_range_box(16, 17).kernel == route_range(16, 33).kernel &&
+              route_range_box(32, 32).kernel == route_range(32, 64).kernel &&
+              route_range_box(32, 32).step == route_range(32, 64).step);
+
 // The slice plan of the batch sum (qpb_kkt_bwd_sum.hip): `slots` consecutive
 // slices of `per` QPs, the last one shorter; one wavefront and one workspace
 // slot per slice.  A function of the batch size alone -- not of the device --

@@ -21,6 +21,7 @@ compat layer in include/compat/; this module mirrors the batched C-ABI:
     solve_box_shared(H, f, lb, ub) -> qpb_solve_box_shared (a box solve with ONE H (n, n) for the whole batch, n <= 128)
     solve_box_shared_backward(H, sol, gx) -> qpb_solve_box_shared_backward (its gradients, gH (n, n) summed over the batch, n <= 32)
     solve_range(H, f, A, bl, bu, meq) -> qpb_solve_range (two-sided rows bl <= A x <= bu, signed lam; n <= 32, m <= 64)
+    solve_range_box(H, f, G, bl, bu, lb, ub, meq) -> qpb_solve_range_box (those rows beside lb <= x <= ub; mg + n <= 64)
     ref_solve(mode, P, q, x0)  -> qpb_ref_solve   (qp_solvers.c replicas)
     qf_eval(P, q, r, x)        -> qpb_qf_eval     (qp.c:9-27)
     ref_generate(n, B, seed)   -> qpb_ref_generate (the reference generator, bit for bit)
@@ -126,6 +127,10 @@ _lib.qpb_solve_range.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_
 _lib.qpb_solve_range.restype = ctypes.c_int
 _lib.qpb_solve_range_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_range_host.restype = ctypes.c_int
+_lib.qpb_solve_range_box.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 14
+_lib.qpb_solve_range_box.restype = ctypes.c_int
+_lib.qpb_solve_range_box_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 13
+_lib.qpb_solve_range_box_host.restype = ctypes.c_int
 _lib.qpb_solve_range_factored.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_range_factored.restype = ctypes.c_int
 _lib.qpb_solve_range_factored_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
@@ -696,6 +701,75 @@ def solve_range_host(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_t
                                    p(bl) if m else None, p(bu) if m else None, p(x), p(lam), p(act), p(low), p(st),
                                    p(it))
     _check(rc, "qpb_solve_range_host")
+    return RangeSolution(x, lam, act, low, st, it)
+
+
+def solve_range_box(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,
+                    out: RangeSolution | None = None, stream=None) -> RangeSolution:
+    """Batched min 1/2 x^T H x + f^T x s.t. G[:meq] x = bu[:meq], bl[meq:] <= G[meq:] x <= bu[meq:],
+    lb <= x <= ub on the GPU (qpb_solve_range_box): qpOASES's and OSQP's whole form.
+
+    ``G`` is (B, mg, n), or (mg, n) for the whole batch, or None (mg = 0: a box
+    alone); ``bl``, ``bu`` are (B, mg) and ``lb``, ``ub`` (B, n).  Any of the
+    four may be None -- that side is absent everywhere -- but not all of them.
+    Every output is, bit for bit, ``solve_range``'s on the materialised
+    ``[G; I]``, ``[bl; lb]``, ``[bu; ub]``, which is never built: ``lam`` is
+    (B, mg + n), the rows first and then variable j at mg + j (>= 0 at ``ub``,
+    <= 0 at ``lb``), ``active`` and ``lower`` have ceil((mg + n) / 32) words.
+    A 2-D ``H`` and / or ``G`` is one matrix for the batch, as in ``solve_range``.
+    n <= 32 and mg + n <= 64."""
+    import torch
+    if bl is None and bu is None and lb is None and ub is None:
+        raise ValueError("qpb.solve_range_box needs at least one of bl, bu, lb and ub")
+    if not (H.is_cuda and f.is_cuda):
+        raise ValueError("qpb.solve_range_box expects CUDA (HIP) tensors; use solve_range_box_host for numpy")
+    B, n = f.shape
+    mg = 0 if G is None else G.shape[-2]
+    for t in (H, f, G, bl, bu, lb, ub):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != f.device):
+            raise ValueError("inputs must be contiguous float64 tensors on one CUDA device")
+    shared = (SHARED_H if H.dim() == 2 else 0) | (SHARED_A if mg and G.dim() == 2 else 0)
+    if (tuple(H.shape) not in ((n, n), (B, n, n)) or (mg and tuple(G.shape) not in ((mg, n), (B, mg, n)))
+            or any(t is not None and tuple(t.shape) != (B, mg) for t in (bl, bu))
+            or any(t is not None and tuple(t.shape) != (B, n) for t in (lb, ub))):
+        raise ValueError("shape mismatch")
+    if out is None:
+        out = _empty_range_solution(B, n, mg + n, f.device)
+    d = Desc(n, mg, B, max_iter, 0, feas_tol)
+    opt = lambda t: _ptr(t) if t is not None and t.numel() else None  # noqa: E731
+    rc = _lib.qpb_solve_range_box(ctypes.byref(d), int(meq), shared, _ptr(H), _ptr(f), opt(G), opt(bl), opt(bu),
+                                  opt(lb), opt(ub), _ptr(out.x), _ptr(out.lam), _ptr(out.active), _ptr(out.lower),
+                                  _ptr(out.status), _ptr(out.iters), _stream_ptr(stream))
+    _check(rc, "qpb_solve_range_box")
+    return out
+
+
+def solve_range_box_host(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max_iter: int = 0,
+                         feas_tol: float = 0.0) -> RangeSolution:
+    """numpy in / numpy out (qpb_solve_range_box_host): ``solve_range_box`` with host arrays."""
+    import numpy as np
+    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+    H, f, G, bl, bu, lb, ub = (c(a) for a in (H, f, G, bl, bu, lb, ub))
+    B, n = f.shape
+    mg = 0 if G is None else G.shape[-2]
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if mg and G.ndim == 2 else 0)
+    if (H.shape not in ((n, n), (B, n, n)) or (mg and G.shape not in ((mg, n), (B, mg, n)))
+            or any(t is not None and t.shape != (B, mg) for t in (bl, bu))
+            or any(t is not None and t.shape != (B, n) for t in (lb, ub))):
+        raise ValueError("shape mismatch")
+    m = mg + n
+    w = (m + 31) // 32
+    x = np.zeros((B, n))
+    lam = np.zeros((B, m))
+    act = np.zeros((B, w), dtype=np.uint32)
+    low = np.zeros((B, w), dtype=np.uint32)
+    st = np.zeros(B, dtype=np.int32)
+    it = np.zeros(B, dtype=np.int32)
+    d = Desc(n, mg, B, max_iter, 0, feas_tol)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_range_box_host(ctypes.byref(d), int(meq), shared, p(H), p(f), p(G), p(bl), p(bu), p(lb),
+                                       p(ub), p(x), p(lam), p(act), p(low), p(st), p(it))
+    _check(rc, "qpb_solve_range_box_host")
     return RangeSolution(x, lam, act, low, st, it)
 
 

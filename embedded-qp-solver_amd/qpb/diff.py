@@ -36,6 +36,11 @@ on the range solve's outputs, its ``gb`` routed to ``bl`` or ``bu`` by the
 forward and solves with ``qpb.solve_range_factored``; the backward is the
 factored one in the same way.
 
+``solve_range_box(H, f, G, bl, bu, lb, ub, meq)`` is ``qpb.solve_range_box`` --
+those rows beside variable bounds, no identity rows in G -- with gradients for
+H, f, G and the four bounds.  Only the backward assembles ``[G; I]``, for
+``qpb.solve_backward`` (or the shared one); a native backward is a follow-up.
+
 ``solve_dual(H, f, A, b, meq)`` and ``solve_range_dual(H, f, A, bl, bu, meq)``
 return ``(x, lam, status)`` with x AND lam differentiable: the backward is
 ``qpb.solve_backward_dual`` (qpb_solve_backward_dual, the same KKT system with
@@ -178,6 +183,65 @@ class RangeQPFunction(torch.autograd.Function):
             if want[4]:
                 gbu = torch.where(low, zero, gb)
         return gH, gf, gA, gbl, gbu, None, None, None, None
+
+
+class RangeBoxQPFunction(torch.autograd.Function):
+    """x*(H, f, G, bl, bu, lb, ub) of min 1/2 x'Hx + f'x s.t. G[:meq] x = bu[:meq],
+    bl[meq:] <= G[meq:] x <= bu[meq:], lb <= x <= ub."""
+
+    @staticmethod
+    def forward(ctx, H, f, G, bl, bu, lb, ub, meq, max_iter, feas_tol):
+        c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+        H, f, G, bl, bu, lb, ub = (c(t) for t in (H, f, G, bl, bu, lb, ub))
+        # above n = 32 or mg + n = 64 this raises QPBError(ERR_UNSUPPORTED)
+        sol = qpb.solve_range_box(H, f, G, bl, bu, lb, ub, meq, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.prefactor = False
+        ctx.mg = 0 if G is None else G.shape[-2]
+        ctx.has = (True, True, G is not None) + tuple(t is not None for t in (bl, bu, lb, ub))
+        ctx.save_for_backward(H, G, sol.x, sol.lam, sol.active, sol.lower, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        H, G, x, lam, active, lower, status = ctx.saved_tensors
+        want = [w and has for w, has in zip(ctx.needs_input_grad[:7], ctx.has)]
+        wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if any(want[3:]) else [])
+        if not wanted:
+            return (None,) * 10
+        # the materialised A' = [G; I] exists here only: (mg + n, n) for one G (or
+        # none), B x (mg + n) x n for a batched one
+        B, n = x.shape
+        mg = ctx.mg
+        eye = torch.eye(n, dtype=x.dtype, device=x.device)
+        if G is None:
+            A = eye
+        elif G.dim() == 2:
+            A = torch.cat([G, eye], dim=0)
+        else:
+            A = torch.cat([G, eye.expand(B, n, n)], dim=1)
+        ctx.shared = H.dim() == 2 or A.dim() == 2
+        sol = qpb.Solution(x, lam, active, status, None)
+        gH, gf, gA, gb = _backward(ctx, H, A.contiguous(), sol, gx.contiguous(), wanted)
+        gG = None if gA is None else gA[..., :mg, :]
+        gbl = gbu = glb = gub = None
+        if gb is not None:
+            # as solve_range routes its gb: an element goes to the lower bound where
+            # the `lower` bit is set (never on an equality), to the upper one elsewhere;
+            # columns < mg are the rows', the others the variables'
+            rows = torch.arange(mg + n, device=gb.device)
+            low = ((lower[:, rows // 32] >> (rows % 32)) & 1).bool()
+            zero = torch.zeros_like(gb)
+            to_lo, to_hi = torch.where(low, gb, zero), torch.where(low, zero, gb)
+            if want[3]:
+                gbl = to_lo[:, :mg]
+            if want[4]:
+                gbu = to_hi[:, :mg]
+            if want[5]:
+                glb = to_lo[:, mg:]
+            if want[6]:
+                gub = to_hi[:, mg:]
+        return gH, gf, gG, gbl, gbu, glb, gub, None, None, None
 
 
 def _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted):
@@ -383,6 +447,22 @@ def solve_range(H, f, A, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: f
         if H.dim() != 2 or A.dim() != 2:
             raise ValueError("prefactor=True needs a 2-D H (n, n) and a 2-D A (m, n): one matrix for the batch")
     return RangeQPFunction.apply(H, f, A, bl, bu, int(meq), int(max_iter), float(feas_tol), bool(prefactor))
+
+
+def solve_range_box(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0):
+    """Differentiable batched solve with two-sided rows beside variable bounds
+    (``qpb.solve_range_box`` with gradients): returns ``(x, status)``; ``x``
+    carries gradients to whichever of H, f, G, bl, bu, lb and ub require them.
+    The forward never builds ``[G; I]``.  The backward does, inside
+    ``backward()`` only -- B x (mg+n) x n for a batched G, (mg+n) x n for a 2-D
+    one -- and runs ``qpb.solve_backward`` (``qpb.solve_shared_backward`` with a
+    2-D H or G) on it: ``G.grad`` is its first mg rows (one summed (mg, n)
+    matrix for a 2-D G), and its ``gb`` goes to ``bl`` / ``bu`` / ``lb`` / ``ub`` by
+    the ``lower`` bits exactly as ``solve_range`` routes it.  A bound passed as
+    None gets no gradient.  A native backward without ``[G; I]`` is a follow-up.
+    n <= 32 and mg + n <= 64: above that the forward raises
+    ``QPBError(ERR_UNSUPPORTED)``."""
+    return RangeBoxQPFunction.apply(H, f, G, bl, bu, lb, ub, int(meq), int(max_iter), float(feas_tol))
 
 
 def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):

@@ -20,6 +20,7 @@
  *   ... a box solve with that H factored ONCE              qpb_factor_box, qpb_solve_box_factored
  *   ... with that H and A factored ONCE                     qpb_factor_shared, qpb_solve_factored
  *   ... with two-sided rows bl <= A x <= bu                 qpb_solve_range
+ *   ... two-sided rows beside variable bounds lb <= x <= ub   qpb_solve_range_box
  *   ... two-sided rows on the H and A factored once          qpb_solve_range_factored
  *   ... differentiated on the H and A factored once           qpb_factor_shared_backward, qpb_solve_factored_backward
  *   ... that, and the box backward, for a loss that reads lam  qpb_solve_factored_backward_dual, qpb_solve_box_backward_dual
@@ -595,10 +596,11 @@ int qpb_solve_backward_dual_host(const qpb_desc *desc, int32_t shared,
  * QPB_ERR_INVALID_ARG (H, f, x and status always; with m > 0 A, lam, active and
  * at least one of bl and bu); a missing device last.
  * Limits: the two wavefront-level classes, n <= 16 with m <= 32 and n <= 32
- * with m <= 64.  Follow-ups: the n <= 128 Gram class, QPB_FLAG_MIXED,
- * qpb_solve_sections and a range form of qpb_solve_box (general rows beside a
- * box) have no range form.  With one H and A for every call of a loop, the
- * set-up need not be repeated per QP: qpb_solve_range_factored, below.
+ * with m <= 64.  Follow-ups: the n <= 128 Gram class, QPB_FLAG_MIXED and
+ * qpb_solve_sections have no range form.  Rows beside variable bounds
+ * lb <= x <= ub need no rows of the identity in A: qpb_solve_range_box, below.
+ * With one H and A for every call of a loop, the set-up need not be repeated
+ * per QP: qpb_solve_range_factored, below.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_range(const qpb_desc *desc, int32_t meq, int32_t shared,
 		    const double *H, const double *f, const double *A,
@@ -612,6 +614,60 @@ int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
 			 const double *bl, const double *bu, double *x,
 			 double *lam, uint32_t *active, uint32_t *lower,
 			 int32_t *status, int32_t *iters);
+
+/* Two-sided rows beside variable bounds, qpOASES's and OSQP's whole form:
+ *   min 1/2 x^T H x + f^T x   s.t.   g_i x = bu_i            (rows i < meq; bl_i is not read)
+ *                                    bl_i <= g_i x <= bu_i   (rows meq <= i < mg)
+ *                                    lb_j <= x_j <= ub_j     (every variable j < n)
+ * desc->m is mg, the number of general rows; mg = 0 is legal, and G may then be
+ * NULL.  G is mg x n per QP (one matrix for the batch with QPB_SHARED_A), bl and
+ * bu mg per QP, lb and ub n per QP.  Any of the four bound arrays may be NULL:
+ * that side is absent everywhere; at least one must be given.
+ * Specification: the materialised problem.  For every QP every output equals,
+ * bit for bit, what qpb_solve_range(meq, shared) writes on m' = mg + n rows,
+ * A' = [G; I_n], bl' = [bl; lb], bu' = [bu; ub] (a NULL half of bl' or bu' being
+ * -inf or +inf), in that call's layouts with m':
+ *   lam     mg + n per QP: the rows first, then variable j at mg + j, >= 0 at
+ *           ub_j and <= 0 at lb_j
+ *   active, lower   ceil((mg + n) / 32) words per QP, row i at bit i and
+ *           variable j at bit mg + j; lower may be NULL
+ * Every sentence of qpb_solve_range's contract therefore holds unchanged: what
+ * is written at every status; NaN and +-inf bounds as absent sides; crossed
+ * bounds (lb_j > ub_j beyond the threshold is QPB_INFEASIBLE from the set-up); a
+ * pinned variable lb_j == ub_j as a zero-width row; lower a subset of active; a
+ * QP's outputs depend on its own inputs only; the default max_iter is
+ * 4 (n + m') + 8.  active and lam go to qpb_solve_backward together with a
+ * materialised A' (a native backward without A' is a follow-up).
+ * What the call saves is A' itself: the identity's rows are made in registers by
+ * the BX forms of the range kernels (qpb_gi.hip, qpb_gi_wave.hip), neither
+ * allocated nor filled by the caller, nor read by the kernel, nor gathered again
+ * for x -- n n doubles per QP, 2 KB at n = 16.
+ * Errors, in order: the descriptor as qpb_solve, with m = mg; meq < 0,
+ * desc->flags != 0, a bit of `shared` outside QPB_SHARED_H | QPB_SHARED_A, each
+ * QPB_ERR_INVALID_ARG; n > 32 or mg + n > 64 QPB_ERR_UNSUPPORTED; meq > mg
+ * QPB_ERR_INVALID_ARG; batch == 0 returns 0 before the pointers are looked at;
+ * missing pointers QPB_ERR_INVALID_ARG (H, f, x, lam, active and status always;
+ * G with mg > 0; at least one of bl, bu, lb and ub); a missing device last.
+ * Limits: the two wavefront-level classes by the materialised shape, n <= 16
+ * with mg + n <= 32 and n <= 32 with mg + n <= 64.  Follow-ups: the n <= 128
+ * Gram class, a factored form (with H and G shared, qpb_factor_shared on
+ * [G; I] serves qpb_solve_range_factored today), QPB_FLAG_MIXED and a native
+ * backward.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_range_box(const qpb_desc *desc, int32_t meq, int32_t shared,
+			const double *H, const double *f, const double *G,
+			const double *bl, const double *bu, const double *lb,
+			const double *ub, double *x, double *lam,
+			uint32_t *active, uint32_t *lower, int32_t *status,
+			int32_t *iters, void *stream);
+
+/* Same with host pointers, as qpb_solve_host (a shared operand is one matrix). */
+int qpb_solve_range_box_host(const qpb_desc *desc, int32_t meq, int32_t shared,
+			     const double *H, const double *f, const double *G,
+			     const double *bl, const double *bu,
+			     const double *lb, const double *ub, double *x,
+			     double *lam, uint32_t *active, uint32_t *lower,
+			     int32_t *status, int32_t *iters);
 
 /* qpb_solve_range(shared = QPB_SHARED_H | QPB_SHARED_A) without the per-QP
  * set-up: two-sided rows on a buffer of qpb_factor_shared for (desc->n,
@@ -894,8 +950,8 @@ int qpb_solve_box_backward_host(const qpb_desc *desc, const double *H,
  * This call factors H per QP on purpose (bit-for-bit equality with
  * qpb_solve_box is its test); with the shared H factored ONCE, so that L and
  * L^-T are the same numbers for every QP: qpb_factor_box and
- * qpb_solve_box_factored, below (n <= 32).  Follow-up: general rows beside a
- * box.
+ * qpb_solve_box_factored, below (n <= 32).  General rows beside a box, with
+ * one H or one per QP: qpb_solve_range_box, above (n <= 32, mg + n <= 64).
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_box_shared(const qpb_desc *desc, const double *H, const double *f,
 			 const double *lb, const double *ub, double *x,
