@@ -1368,6 +1368,151 @@ extern "C" int qpb_solve_range_box_host(const qpb_desc *d, int32_t meq, int32_t 
   return 0;
 }
 
+// ---- the backward of two-sided rows beside variable bounds -------------------------
+// qpb_solve_range_box_backward's argument rules after check_desc (d->m is mg), up to batch == 0
+static int check_range_box_bwd(const qpb_desc *d, int32_t shared) {
+  if (d->flags != 0)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_range_box_backward: flags must be 0 (got %d)", d->flags);
+  if (shared & ~(QPB_SHARED_H | QPB_SHARED_A))
+    return fail(QPB_ERR_INVALID_ARG,
+                "qpb_solve_range_box_backward: shared must be a combination of QPB_SHARED_H and QPB_SHARED_A (got %d)",
+                shared);
+  if (qpb::route_bwd_range_box(d->n, d->m).step == 0)
+    return fail(QPB_ERR_UNSUPPORTED,
+                "qpb_solve_range_box_backward: n=%d mg=%d outside the backward kernels with a box (n<=%d, mg+n<=%d)",
+                d->n, d->m, qpb::kBwdRangeBoxMaxN, qpb::kBwdRangeBoxMaxRows);
+  return 0;
+}
+// ... and the pointers (device or host)
+static int check_range_box_bwd_arrays(const qpb_desc *d, const double *H, const double *G, const double *x,
+                                      const double *lam, const uint32_t *active, const uint32_t *lower,
+                                      const double *gx, const double *gH, const double *gf, const double *gG,
+                                      const double *gbl, const double *gbu, const double *glb, const double *gub) {
+  if (!H || !x || !lam || !active || !gx)
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_range_box_backward: H, x, lam, active and gx are required");
+  if (d->m > 0 && !G) return fail(QPB_ERR_INVALID_ARG, "qpb_solve_range_box_backward: G is required when mg > 0");
+  if (!lower && (gbl || glb))
+    return fail(QPB_ERR_INVALID_ARG, "qpb_solve_range_box_backward: lower is required when gbl or glb is given");
+  if (!gH && !gf && !glb && !gub && !(d->m > 0 && (gG || gbl || gbu)))
+    return fail(QPB_ERR_INVALID_ARG,
+                "qpb_solve_range_box_backward: at least one of gH, gf, gG, gbl, gbu, glb and gub is required");
+  return 0;
+}
+
+extern "C" int qpb_solve_range_box_backward(const qpb_desc *d, int32_t shared, const double *H, const double *G,
+                                            const double *x, const double *lam, const uint32_t *active,
+                                            const uint32_t *lower, const int32_t *status, const double *gx,
+                                            const double *glam, double *gH, double *gf, double *gG, double *gbl,
+                                            double *gbu, double *glb, double *gub, void *stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_range_box_bwd(d, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  rc = check_range_box_bwd_arrays(d, H, G, x, lam, active, lower, gx, gH, gf, gG, gbl, gbu, glb, gub);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  shared = shared_of(d, shared);  // (mg == 0: no G to share)
+  // the kernels count all the rows, m' = mg + n: the class and the chunks of the call on [G; I]
+  const qpb::Route r = qpb::route_bwd_range_box(d->n, d->m);
+  const long long n = d->n, mg = d->m, m = mg + n, B = d->batch, w = (m + 31) / 32;
+  if (mg == 0) gG = gbl = gbu = nullptr;  // ignored
+  const long long sH = (shared & QPB_SHARED_H) ? 0 : n * n, sG = (shared & QPB_SHARED_A) ? 0 : mg * n;
+  // the gradients pass 2 sums; pass 1 is launched without them
+  double *const sumH = (shared & QPB_SHARED_H) ? gH : nullptr, *const sumG = (shared & QPB_SHARED_A) ? gG : nullptr;
+  double *const gH1 = (shared & QPB_SHARED_H) ? nullptr : gH, *const gG1 = (shared & QPB_SHARED_A) ? nullptr : gG;
+  const hipStream_t st = (hipStream_t)stream;
+  qpb_desc dm = *d;
+  dm.m = (int32_t)m;
+  // pass 1 over the batch in chunks; gf1 is the caller's, or the workspace's where pass 2 needs it, gbw the workspace's
+  auto pass1 = [&](double *gf1, double *gbw) {
+    return qpb::for_each_chunk(
+        B, r.step,
+        [&](long long count, const double *Hc, const double *Gc, const double *xc, const double *lc,
+            const uint32_t *ac, const uint32_t *wc, const int32_t *sc, const double *gxc, const double *glc,
+            double *gHc, double *gfc, double *gGc, double *gblc, double *gbuc, double *glbc, double *gubc,
+            double *gbwc) {
+          qpb_desc c = dm;
+          c.batch = count;
+          const hipError_t e = qpb_launch_kkt_bwd_range_box(&c, (int)mg, sH, sG, Hc, Gc, xc, lc, ac, wc, sc, gxc, glc,
+                                                            gHc, gfc, gGc, gblc, gbuc, glbc, gubc, gbwc, st);
+          return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_range_box_backward launch");
+        },
+        qpb::required(H, sH), qpb::optional(G, sG), qpb::required(x, n), qpb::required(lam, m),
+        qpb::required(active, w), qpb::optional(lower, w), qpb::optional(status, 1), qpb::required(gx, n),
+        qpb::optional(glam, m), qpb::optional(gH1, n * n), qpb::optional(gf1, n), qpb::optional(gG1, mg * n),
+        qpb::optional(gbl, mg), qpb::optional(gbu, mg), qpb::optional(glb, n), qpb::optional(gub, n),
+        qpb::optional(gbw, mg));
+  };
+  if (!sumH && !sumG) return pass1(gf, nullptr);  // the summed gradients are not wanted: pass 1 alone
+  // workspace: the slots, then dx (B n) where gf is not given, then pass 1's
+  // unrouted gb of the rows of G (B mg) where gG is summed
+  const long long slot_doubles = qpb::sum_plan(B).slots * qpb::sum_slot_doubles(d->n, (int)mg);
+  const long long ws_dx = gf ? 0 : B * n, ws_gb = sumG ? B * mg : 0;
+  const hipError_t e = qpb_with_workspace(st, (size_t)(slot_doubles + ws_dx + ws_gb) * 8, [&](void *ws) {
+    double *const slots = (double *)ws;
+    double *const dx = gf ? gf : slots + slot_doubles;
+    double *const gbw = sumG ? slots + slot_doubles + ws_dx : nullptr;
+    rc = pass1(dx, gbw);
+    if (rc) return hipSuccess;  // reported through rc
+    return qpb_launch_kkt_bwd_sum_range_box(&dm, (int)mg, x, dx, gbw, lam, active, status, slots, sumH, sumG, st);
+  });
+  if (rc) return rc;
+  return e == hipSuccess ? 0 : hip_fail(e, "qpb_solve_range_box_backward sum launch");
+}
+
+extern "C" int qpb_solve_range_box_backward_host(const qpb_desc *d, int32_t shared, const double *H, const double *G,
+                                                 const double *x, const double *lam, const uint32_t *active,
+                                                 const uint32_t *lower, const int32_t *status, const double *gx,
+                                                 const double *glam, double *gH, double *gf, double *gG, double *gbl,
+                                                 double *gbu, double *glb, double *gub) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  rc = check_range_box_bwd(d, shared);
+  if (rc) return rc;
+  if (d->batch == 0) return 0;
+  // host pointers: the same rules
+  rc = check_range_box_bwd_arrays(d, H, G, x, lam, active, lower, gx, gH, gf, gG, gbl, gbu, glb, gub);
+  if (rc) return rc;
+  rc = check_device();
+  if (rc) return rc;
+  shared = shared_of(d, shared);
+  const size_t B = (size_t)d->batch, n = d->n, mg = d->m, m = mg + n, w = (m + 31) / 32;
+  const size_t BH = (shared & QPB_SHARED_H) ? 1 : B, BG = (shared & QPB_SHARED_A) ? 1 : B;
+  DevBuf dH, dG, dx, dl, da, dw, ds, dg, dgl, oH, of, oG, obl, obu, olb, oub;
+  HIPCHK(up(dH, H, BH * n * n * 8), "H");
+  HIPCHK(up(dG, mg ? G : nullptr, BG * mg * n * 8), "G");
+  HIPCHK(up(dx, x, B * n * 8), "x");
+  HIPCHK(up(dl, lam, B * m * 8), "lam");
+  HIPCHK(up(da, active, B * w * 4), "active");
+  HIPCHK(up(dw, lower, B * w * 4), "lower");
+  HIPCHK(up(ds, status, B * 4), "status");
+  HIPCHK(up(dg, gx, B * n * 8), "gx");
+  HIPCHK(up(dgl, glam, B * m * 8), "glam");
+  HIPCHK(alloc(oH, gH, BH * n * n * 8), "gH");
+  HIPCHK(alloc(of, gf, B * n * 8), "gf");
+  HIPCHK(alloc(oG, mg ? gG : nullptr, BG * mg * n * 8), "gG");
+  HIPCHK(alloc(obl, gbl, B * mg * 8), "gbl");
+  HIPCHK(alloc(obu, gbu, B * mg * 8), "gbu");
+  HIPCHK(alloc(olb, glb, B * n * 8), "glb");
+  HIPCHK(alloc(oub, gub, B * n * 8), "gub");
+  rc = qpb_solve_range_box_backward(d, shared, (double *)dH.p, (double *)dG.p, (double *)dx.p, (double *)dl.p,
+                                    (uint32_t *)da.p, (uint32_t *)dw.p, (int32_t *)ds.p, (double *)dg.p,
+                                    (double *)dgl.p, (double *)oH.p, (double *)of.p, (double *)oG.p, (double *)obl.p,
+                                    (double *)obu.p, (double *)olb.p, (double *)oub.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize(), "qpb_solve_range_box_backward_host kernel");
+  HIPCHK(down(gH, oH, BH * n * n * 8), "gH D2H");
+  HIPCHK(down(gf, of, B * n * 8), "gf D2H");
+  HIPCHK(down(mg ? gG : nullptr, oG, BG * mg * n * 8), "gG D2H");
+  HIPCHK(down(gbl, obl, B * mg * 8), "gbl D2H");
+  HIPCHK(down(gbu, obu, B * mg * 8), "gbu D2H");
+  HIPCHK(down(glb, olb, B * n * 8), "glb D2H");
+  HIPCHK(down(gub, oub, B * n * 8), "gub D2H");
+  return 0;
+}
+
 // ---- two-sided rows on a factor buffer ------------------------------------------
 // qpb_solve_range_factored's argument rules after check_desc, up to batch == 0
 static int check_range_factored(const qpb_desc *d, int32_t meq) {
@@ -2050,4 +2195,4 @@ extern "C" const char *qpb_last_error(void) { return g_err; }
 
 // the hot kernel revision is part of the string: profiles/pmc_traffic.json is
 // only trusted for the revision it was measured on (bench.py)
-extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed; kkt_bwd_fact v1.0: qpb_solve_factored_backward for n <= 32 and m <= 64, a shared H and A factored once by the backward kernels' own set-up into a buffer of the backward's own that holds L, 1 / L_kk, D = A L^-T and the sweep's multipliers, the factored forms of kkt_bwd take u from them by the set-up's own operations, outputs bit for bit those of qpb_solve_shared_backward; box_shared v1.0: qpb_solve_box_shared for n <= 128 and qpb_solve_box_shared_backward for n <= 32, one H for a batch of box QPs read from one copy through a run-time QP stride in the SH forms of gi_box, gi_wave's and gi_gram's BOX kernels and kkt_bwd_box, outputs bit for bit those of qpb_solve_box and qpb_solve_box_backward on copies, gH summed over the batch by kkt_bwd_sum at m = 0; box_fact v1.0: qpb_factor_box and qpb_solve_box_factored for n <= 32, the one H of a batch of box QPs factored once by the class's own load and sweep into a buffer that holds L, the rows of L^-T and their squared norms in the order the solve's lanes load them and neither H nor A, the factored forms of gi_box and of gi_wave's BOX kernel start from a forward substitution for y = L^-1 f with e = L^-T y accumulated alongside and the slacks ub + e and -lb - e in place of the set-up sweep, the lower bounds' rows negated as they are loaded; gi_range_box v1.0: qpb_solve_range_box for n <= 32 and mg + n <= 64, two-sided rows beside variable bounds lb <= x <= ub in the BX forms of the RG forms of gi_dense and gi_wave, the identity's rows made in registers where the materialised [G; I] would put them and added as lam e_j in the x recovery, outputs bit for bit those of qpb_solve_range on the materialised problem)"; }
+extern "C" const char *qpb_version(void) { return "qpb 0.14 (gfx950; gi_dense v11.7: a scalar base per group of four QPs and 32-bit lane offsets for every load and store (outputs bit for bit those of gi_dense v11.6), DROP argmin taken in the DROP, back-substitution tests grouped 15..8 / 7..4 / 3..1, x gather as one DPP-fused 32-bit add per row, dual steepest-edge select -s/|D[r,q:]| with a nonzero key floor, dependency scale clamped to FLT_MAX, setup slacks from the sweep's DPP-read f, output stores under the A-row loads, DPP-fused slack product and Householder update, Householder product as u + alpha D[:,q], exact ratio step, one-trip loads and x gather, 3 waves/SIMD and 12 per CU (12,608 B of LDS per wave: the exchange row in R's column 0, Givens parameters in registers), built without machine LICM; gi_box v2.2: lb <= x <= ub, A implicit, dual steepest-edge select with a nonzero key floor, DPP-fused slack and Householder products, one-pass R column shift, 12 waves per CU; gi_wave v6.7 (+ BOX, n <= 32; absent bounds as +inf slacks): x solves with the components captured in LDS (no lane masks, no SGPR spills), dual steepest-edge select with a nonzero key floor, ratio reduction only when a partial step is possible, active A rows for x gathered 16 at a time, DPP-fused sweep, slack product, Householder update and back substitution (no LDS vector reads), Householder product as u + alpha D[:,q], odd-stride R with the exchange row in its column 0 (12 waves per CU), one-trip A gather for x, split setup sweep, 3 waves/SIMD; gi_gram v4.5 (+ BOX, n <= 128: qpb_solve_box with A generated in place) n<=128 on fp64 MFMA, no next-QP prefetch, lane ids opaque per iteration (2 VGPR spills instead of 29), active set as Q1 rows and Z = R^{-1} (parallel passes only), |u|^2 published with the key, broadcast row products, conflict-free diagonal-tile inverses, one-trip loads, cached workspace launched under its lock; ref v6: n <= 1024 (above 128: 1024-thread workgroups, the matrices in a global workspace slice), 64 < n <= 128 one LDS matrix per workgroup (LU, W / V, P in turn), LU rows staged for the solves, branch-free chunked sums; gi_eq v1.0: qpb_solve_eq for n <= 32 and m <= 64, equality rows 0 .. meq-1 in the EQ forms of gi_dense and gi_wave, taken first and never dropped, sign chosen at selection, free multipliers, consistent dependent rows left out; kkt_bwd v1.1: qpb_solve_backward for n <= 32 and m <= 64, gradients of a solve through its KKT system at fixed active set, H factored and the active rows of A L^-T orthogonalised in row order (two Gram-Schmidt passes, and two projections of L^-1 g: A_W dx = 0 holds at cond(H) = 1e10 with |W| = n), four QPs per wavefront for n <= 16 and m <= 32, one per wavefront above; kkt_bwd_box v1.0: qpb_solve_box_backward for n <= 32, gradients of a box solve for H, f, lb and ub at fixed active set, one Cholesky of H with the fixed variables' rows and columns replaced by the identity (no gather, no A, no lam), r = gx + H dx on the active bounds, four QPs per wavefront for n <= 16, one per wavefront above; gi_shared v1.0: qpb_solve_shared for n <= 32 and m <= 64, one H and / or one A for the whole batch read from one copy through run-time QP strides in the SH forms of gi_dense and gi_wave, plain and EQ, outputs bit for bit those of qpb_solve_eq on copies; kkt_bwd_sum v1.0: qpb_solve_shared_backward, the gradient of a shared H or A summed over the batch on the fp64 matrix cores, four QPs per MFMA step, one wave per slice of a plan that depends on the batch size alone, slots added in order by a finish kernel, no atomics; gi_range v1.0: qpb_solve_range for n <= 32 and m <= 64, two-sided rows bl <= A x <= bu in the RG forms of gi_dense and gi_wave (on their EQ and SH forms: equality rows and a shared H or A at run time), one row of D and an orientation bit per row, the row negated in place when its other side is selected, the side kept with the active position through a DROP, signed multipliers in OSQP's convention and a `lower` bit set beside `active`; gi_fact v1.0: qpb_factor_shared and qpb_solve_factored for n <= 32 and m <= 64, one shared H and A factored once by the class's own load and sweep into a buffer that holds L, D = A L^-T, the rows' norms and A in the order the solve's lanes load them, the factored forms of gi_dense and gi_wave, plain and EQ, start from a forward substitution for y and s = b + D y in place of the set-up sweep; gi_rfact v1.0: qpb_solve_range_factored for n <= 32 and m <= 64, two-sided rows on the same factor buffer in the RG forms of the factored kernels, thresholds from the stored |a_r| bit for bit the range form's, a lower-only row's stored row of D negated before the slacks are formed; kkt_bwd_fact v1.0: qpb_solve_factored_backward for n <= 32 and m <= 64, a shared H and A factored once by the backward kernels' own set-up into a buffer of the backward's own that holds L, 1 / L_kk, D = A L^-T and the sweep's multipliers, the factored forms of kkt_bwd take u from them by the set-up's own operations, outputs bit for bit those of qpb_solve_shared_backward; box_shared v1.0: qpb_solve_box_shared for n <= 128 and qpb_solve_box_shared_backward for n <= 32, one H for a batch of box QPs read from one copy through a run-time QP stride in the SH forms of gi_box, gi_wave's and gi_gram's BOX kernels and kkt_bwd_box, outputs bit for bit those of qpb_solve_box and qpb_solve_box_backward on copies, gH summed over the batch by kkt_bwd_sum at m = 0; box_fact v1.0: qpb_factor_box and qpb_solve_box_factored for n <= 32, the one H of a batch of box QPs factored once by the class's own load and sweep into a buffer that holds L, the rows of L^-T and their squared norms in the order the solve's lanes load them and neither H nor A, the factored forms of gi_box and of gi_wave's BOX kernel start from a forward substitution for y = L^-1 f with e = L^-T y accumulated alongside and the slacks ub + e and -lb - e in place of the set-up sweep, the lower bounds' rows negated as they are loaded; gi_range_box v1.0: qpb_solve_range_box for n <= 32 and mg + n <= 64, two-sided rows beside variable bounds lb <= x <= ub in the BX forms of the RG forms of gi_dense and gi_wave, the identity's rows made in registers where the materialised [G; I] would put them and added as lam e_j in the x recovery, outputs bit for bit those of qpb_solve_range on the materialised problem; kkt_bwd_range_box v1.0: qpb_solve_range_box_backward for n <= 32 and mg + n <= 64, the BX forms of kkt_bwd (plain, shared and with glam) and of kkt_bwd_sum, unit rows made in registers, the gradient of the identity neither computed nor stored, gb routed to the four bound arrays by the lower bits, outputs bit for bit those of qpb_solve_backward_dual on the materialised problem)"; }

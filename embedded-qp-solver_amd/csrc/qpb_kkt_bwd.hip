@@ -122,16 +122,45 @@ struct Multi {
   int T;
   long long stride;
 };
+// BX (qpb_solve_range_box_backward, both kernels, FM == 0, plain and SH, with and
+// without glam): the rows are the mg rows of G and then the n variables' unit
+// rows, m = mg + n in all -- the problem of qpb_solve_backward on A' = [G; I]
+// with A' never in memory.  The pack's last argument, a Box, which only this
+// form has, carries mg, the `lower` bit masks and the outputs that take gb's
+// place.  Ag is G (QP stride mg n, unread at mg == 0); a row >= mg is made in
+// registers where the other forms load it, and from the sweep on no operation
+// differs, so L, D, Q, R, dx and dlam are that call's bits.  gAg is gG: the
+// rows < mg.  An element of gb goes to the lower-side array where the row's
+// `lower` bit is set and to the upper-side one otherwise, +0.0 to the other; gbw
+// (pass 2's, else NULL) takes the rows < mg unrouted.  gbg is not read.
+struct Box {
+  int mg;
+  const uint32_t *lower;          // ceil(m / 32) words per QP, or NULL: every row to the upper side
+  double *gbl, *gbu, *glb, *gub;  // B x mg, B x mg, B x n, B x n; any may be NULL
+  double *gbw;                    // B x mg
+};
 template <class... GL>
 inline constexpr bool tail_is_multi = (std::is_same_v<GL, Multi> || ...);
 template <class... GL>
+inline constexpr bool tail_is_box = (std::is_same_v<GL, Box> || ...);
+template <class... GL>
 inline constexpr bool tail_ok = std::is_same_v<void(GL...), void()> || std::is_same_v<void(GL...), void(const double *)> ||
                                 std::is_same_v<void(GL...), void(Multi)> ||
-                                std::is_same_v<void(GL...), void(const double *, Multi)>;
+                                std::is_same_v<void(GL...), void(const double *, Multi)> ||
+                                std::is_same_v<void(GL...), void(Box)> ||
+                                std::is_same_v<void(GL...), void(const double *, Box)>;
 __device__ __forceinline__ const double *tail_glam(const double *p) { return p; }
 __device__ __forceinline__ const double *tail_glam(const double *p, Multi) { return p; }
 __device__ __forceinline__ Multi tail_multi(Multi mu) { return mu; }
 __device__ __forceinline__ Multi tail_multi(const double *, Multi mu) { return mu; }
+__device__ __forceinline__ const double *tail_glam(const double *p, Box) { return p; }
+__device__ __forceinline__ Box tail_box(Box bx) { return bx; }
+__device__ __forceinline__ Box tail_box(const double *, Box bx) { return bx; }
+// the routed pair of one element of gb: v to the side the row's `lower` bit names, +0.0 to the other
+__device__ __forceinline__ void store_routed(double *lo, double *up, long long e, bool lower, double v) {
+  if (lo) lo[e] = lower ? v : 0.0;
+  if (up) up[e] = lower ? 0.0 : v;
+}
 
 template <int MR, bool N16, bool SH = false, class... FMP, class... GL>
 __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
@@ -142,9 +171,10 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   constexpr bool MU = tail_is_multi<GL...>;
-  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) == 1;
-  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2),
-                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only");
+  constexpr bool BX = tail_is_box<GL...>;
+  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) - (BX ? 1 : 0) == 1;
+  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2) && !(BX && FM != 0),
+                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only; a box beside H and G only");
   __shared__ double lds[QPB * SLOT];
   [[maybe_unused]] int shared = 0;
   if constexpr (SH) {
@@ -165,8 +195,11 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   const int lc = var ? l : n - 1;
   const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
   // m == 0: the (masked) row loads read H
+  [[maybe_unused]] int mg = m;  // BX: the rows of G, of the m = mg + n rows
+  if constexpr (BX) mg = tail_box(glamg...).mg;
+  const int ma = BX ? mg : m;  // the rows in memory at Ag
   const double *Aq =
-      m > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n) : Hq;
+      ma > 0 ? (SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)ma * n : Ag + g * (long long)ma * n) : Hq;
   // (FM == 2: nor does any QP on a buffer whose H was not positive definite)
   const bool ok = form_ok<FM>(statg, g, Hg);
   // a QP that is not QPB_OK takes no trips and stores zeros
@@ -176,7 +209,7 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
   if constexpr (!MU) gv = form_gx<FM>(gxg, g * n + lc);
   [[maybe_unused]] double gl[MR];  // DU: glam of the lane's rows, 0 outside W (whatever it holds there)
   if constexpr (DU && !MU) {
-    const double *__restrict__ glq = (glamg, ...) + g * (long long)m;  // (the form has m > 0)
+    const double *__restrict__ glq = tail_glam(glamg...) + g * (long long)m;  // (the form has m > 0)
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
       const int row = l + NL * r;
@@ -252,9 +285,18 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
       for (int t = 0; t < 8; ++t) {
         // rows past m read a valid row (m == 0: of H) and are zeroed: no branch around a load
         const int row = NL * r + 2 * t + hr;
-        const double2 a = *reinterpret_cast<const double2 *>(&Aq[(row < m ? row : 0) * NL + hc]);
+        const double2 a = *reinterpret_cast<const double2 *>(&Aq[(row < ma ? row : 0) * NL + hc]);
         asm volatile("" ::"v"(a.x), "v"(a.y));
-        av[r][t] = row < m ? a : make_double2(0.0, 0.0);
+        if constexpr (BX) {
+          // a row >= mg is variable row - mg's unit row, made here in place of the load (selected per
+          // component: a select between two double2 objects goes through their addresses, and the
+          // staging arrays then live in scratch)
+          const int j = row - mg;
+          const double u0 = (row < m && j == hc) ? 1.0 : 0.0, u1 = (row < m && j == hc + 1) ? 1.0 : 0.0;
+          av[r][t] = make_double2(row < mg ? a.x : u0, row < mg ? a.y : u1);
+        } else {
+          av[r][t] = row < m ? a : make_double2(0.0, 0.0);
+        }
       }
     stage(hv);
     lds_row16(&base[l * RS], Lr);
@@ -270,12 +312,13 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
       const int row = l + NL * r;
-      const bool rok = row < m;
+      const bool rok = row < ma;
       const int rc = rok ? row : 0;
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
         const double a = Aq[rc * n + (j < n ? j : n - 1)];
-        E[r][j] = (rok && j < n) ? a : 0.0;
+        if constexpr (BX) E[r][j] = (rok && j < n) ? a : (row >= mg && row < m && j == row - mg) ? 1.0 : 0.0;
+        else E[r][j] = (rok && j < n) ? a : 0.0;
       }
     }
   }
@@ -649,9 +692,24 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
 #pragma unroll
   for (int r = 0; r < MR; ++r) {
     const int row = ls + NL * r;
-    if (gbg && lives && row < m) gbg[gs * m + row] = pos[r] >= 0 ? -dl[r] : 0.0;
+    if constexpr (BX) {
+      // (the class has m <= 32: one word of `lower`)
+      const Box bx = tail_box(glamg...);
+      const double v = pos[r] >= 0 ? -dl[r] : 0.0;
+      if (lives && row < m) {
+        const bool lo = bx.lower ? (bx.lower[gs] >> row) & 1u : false;
+        if (row < mg) {
+          store_routed(bx.gbl, bx.gbu, gs * mg + row, lo, v);
+          if (bx.gbw) bx.gbw[gs * mg + row] = v;
+        } else {
+          store_routed(bx.glb, bx.gub, gs * n + (row - mg), lo, v);
+        }
+      }
+    } else {
+      if (gbg && lives && row < m) gbg[gs * m + row] = pos[r] >= 0 ? -dl[r] : 0.0;
+    }
   }
-  const bool wantA = gAg && m > 0;
+  const bool wantA = gAg && ma > 0;
   if (!gHg && !wantA) return;  // wave-uniform
   // the vectors of the outer products, over the dead L
   base[OFF_X + ls] = xo;
@@ -678,13 +736,13 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
       }
     }
     if (wantA && lives) {
-      double *o = gAg + gs * (long long)m * NL;
+      double *o = gAg + gs * (long long)ma * NL;
 #pragma unroll
       for (int r = 0; r < MR; ++r)
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
           const int row = NL * r + 2 * t + hr;
-          if (row < m) {
+          if (row < ma) {
             const double dr = DL[row], lr = LM[row];
             *reinterpret_cast<double2 *>(&o[row * NL + hc]) =
                 make_double2(sym2(dr, x0, lr, d0), sym2(dr, x1, lr, d1));
@@ -701,8 +759,8 @@ __global__ __launch_bounds__(64, 3) void kkt_bwd_dense_kernel(
       }
     }
     if (wantA && lives) {
-      double *o = gAg + gs * (long long)m * n;
-      for (int e = ls; e < m * n; e += NL) {
+      double *o = gAg + gs * (long long)ma * n;
+      for (int e = ls; e < ma * n; e += NL) {
         const int row = e / n, col = e - row * n;
         o[e] = sym2(DL[row], X[col], LM[row], DX[col]);
       }
@@ -754,9 +812,10 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   constexpr int FM = (0 + ... + FMP::value);
   static_assert(sizeof...(FMP) <= 1 && FM >= 0 && FM <= 2 && !(SH && FM != 0), "one form at most, on its own strides");
   constexpr bool MU = tail_is_multi<GL...>;
-  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) == 1;
-  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2),
-                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only");
+  constexpr bool BX = tail_is_box<GL...>;
+  constexpr bool DU = sizeof...(GL) - (MU ? 1 : 0) - (BX ? 1 : 0) == 1;
+  static_assert(tail_ok<GL...> && !(DU && FM == 1) && !(MU && FM != 2) && !(BX && FM != 0),
+                "glam is one array, beside H and A or a buffer of them; T directions on a buffer only; a box beside H and G only");
   __shared__ double lds[W_SIZE];
   // an object of its own: the factorisation's trailing update reads it while
   // it writes L, and the compiler can then batch the reads of an unrolled trip
@@ -773,7 +832,10 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   double *Lm = lds + W_L, *Qm = lds + W_Q;
   double *vb = lds + W_V, *cb = lds + W_C, *ub = lds + W_U, *ir = lds + W_IR, *posb = lds + W_POS;
   const double *Hq = SH ? Hg + ((shared & QPB_SHARED_H) ? 0 : g) * (long long)n * n : Hg + g * (long long)n * n;
-  const double *Aq = SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)m * n : Ag + g * (long long)m * n;
+  [[maybe_unused]] int mg = m;  // BX: the rows of G, of the m = mg + n rows
+  if constexpr (BX) mg = tail_box(glamg...).mg;
+  const int ma = BX ? mg : m;  // the rows in memory at Ag (BX, mg == 0: Ag is never read)
+  const double *Aq = SH ? Ag + ((shared & QPB_SHARED_A) ? 0 : g) * (long long)ma * n : Ag + g * (long long)ma * n;
   const bool ok = form_ok<FM>(statg, g, Hg);
   // the active mask as one 64-bit word (wave-uniform); a QP that is not QPB_OK takes no trips
   const int words = (m + 31) / 32;
@@ -787,7 +849,7 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
       (unsigned)__builtin_amdgcn_readfirstlane((int)W);
   [[maybe_unused]] double glv = 0.0;  // DU: glam of row `lane`, 0 outside W (whatever it holds there)
   if constexpr (DU && !MU) {
-    const double v = (glamg, ...)[g * m + (lane < m ? lane : 0)];  // (the form has m > 0)
+    const double v = tail_glam(glamg...)[g * m + (lane < m ? lane : 0)];  // (the form has m > 0)
     glv = ((W >> lane) & 1ull) ? v : 0.0;
   }
   [[maybe_unused]] const bfct::Layout fy = bfct::layout(FM != 0 ? n : 17, m);  // the wave class's offsets
@@ -920,7 +982,14 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
   for (unsigned long long rem = W; rem != 0; rem &= rem - 1ull) {
     const int r = __builtin_ctzll(rem);
     // row r of D: L d^T = a_r^T, component j at lane j (0 on the padding and the upper lanes)
-    double v = FM == 2 ? (low ? Hg[fy.D + r * WN + lane] : 0.0) : var ? Aq[r * n + lane] : 0.0;
+    double v;
+    if constexpr (BX) {
+      // a row >= mg is variable r - mg's unit row (r is wave-uniform: G is read below mg only)
+      if (r < mg) v = var ? Aq[r * n + lane] : 0.0;
+      else v = lane == r - mg ? 1.0 : 0.0;
+    } else {
+      v = FM == 2 ? (low ? Hg[fy.D + r * WN + lane] : 0.0) : var ? Aq[r * n + lane] : 0.0;
+    }
     if constexpr (FM != 2) {
 #pragma unroll
     for (int k = 0; k < WN; ++k) {
@@ -1096,7 +1165,21 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
     const bool inW = (W >> lane) & 1ull;
     DL[lane] = dl;
     LM[lane] = inW ? lamg[g * m + lane] : 0.0;
-    if (gbg && lane < m) gbg[g * m + lane] = p >= 0 ? -dl : 0.0;
+    if constexpr (BX) {
+      const Box bx = tail_box(glamg...);
+      const double v = p >= 0 ? -dl : 0.0;
+      if (lane < m) {
+        const bool lo = bx.lower ? (bx.lower[g * words + (lane >> 5)] >> (lane & 31)) & 1u : false;
+        if (lane < mg) {
+          store_routed(bx.gbl, bx.gbu, g * mg + lane, lo, v);
+          if (bx.gbw) bx.gbw[g * mg + lane] = v;
+        } else {
+          store_routed(bx.glb, bx.gub, g * n + (lane - mg), lo, v);
+        }
+      }
+    } else {
+      if (gbg && lane < m) gbg[g * m + lane] = p >= 0 ? -dl : 0.0;
+    }
   }
   if (gfg && var) gfg[g * n + lane] = dx;
   wave_lds_sync();
@@ -1107,9 +1190,9 @@ __global__ __launch_bounds__(64) void kkt_bwd_wave_kernel(
       o[e] = 0.5 * sym2(DX[row], X[col], X[row], DX[col]);
     }
   }
-  if (gAg && m > 0) {
-    double *o = gAg + g * (long long)m * n;
-    for (int e = lane; e < m * n; e += 64) {
+  if (gAg && ma > 0) {
+    double *o = gAg + g * (long long)ma * n;
+    for (int e = lane; e < ma * n; e += 64) {
       const int row = e / n, col = e - row * n;
       o[e] = sym2(DL[row], X[col], LM[row], DX[col]);
     }
@@ -1187,6 +1270,47 @@ extern "C" hipError_t qpb_launch_kkt_bwd_dual(const qpb_desc *d, long long strid
                          H, A, x, lam, active, status, gx, gH, gf, gA, gb, d->n, d->m, (long long)d->batch, glam);
     });
   }
+  return hipGetLastError();
+}
+
+// pass 1 of qpb_solve_range_box_backward: the BX forms, of the form the call on
+// A' = [G; I] takes at the same arguments -- plain where both strides are the
+// batched ones and SH otherwise, DU where glam is given
+extern "C" hipError_t qpb_launch_kkt_bwd_range_box(const qpb_desc *d, int mg, long long strideH, long long strideG,
+                                                   const double *H, const double *G, const double *x,
+                                                   const double *lam, const uint32_t *active, const uint32_t *lower,
+                                                   const int32_t *status, const double *gx, const double *glam,
+                                                   double *gH, double *gf, double *gG, double *gbl, double *gbu,
+                                                   double *glb, double *gub, double *gbw, hipStream_t stream) {
+  const int shared = (strideH == 0 ? QPB_SHARED_H : 0) | ((strideG == 0 && mg > 0) ? QPB_SHARED_A : 0);
+  const int mm = d->m | (shared << qpb::bwd::kShShift);
+  const long long blocks = (d->batch + qpb::bwd::QPB - 1) / qpb::bwd::QPB;
+  const bool wave = d->n > 16 || d->m > 32;
+  const qpb::bwd::Box bx{mg, lower, gbl, gbu, glb, gub, gbw};
+  double *no_gb = nullptr;
+  auto go = [&](auto... tail) {
+    if (wave && shared) {
+      hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<true>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, G, x,
+                         lam, active, status, gx, gH, gf, gG, no_gb, d->n, mm, (long long)d->batch, tail...);
+    } else if (wave) {
+      hipLaunchKernelGGL(qpb::bwd::kkt_bwd_wave_kernel<>, dim3((unsigned)d->batch), dim3(64), 0, stream, H, G, x, lam,
+                         active, status, gx, gH, gf, gG, no_gb, d->n, d->m, (long long)d->batch, tail...);
+    } else if (shared) {
+      qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+        hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16(), true>), dim3((unsigned)blocks), dim3(64), 0,
+                           stream, H, G, x, lam, active, status, gx, gH, gf, gG, no_gb, d->n, mm, (long long)d->batch,
+                           tail...);
+      });
+    } else {
+      qpb::row16::dispatch_form(d->n, d->m, [&](auto MR, auto N16, auto) {
+        hipLaunchKernelGGL((qpb::bwd::kkt_bwd_dense_kernel<MR(), N16()>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                           H, G, x, lam, active, status, gx, gH, gf, gG, no_gb, d->n, d->m, (long long)d->batch,
+                           tail...);
+      });
+    }
+  };
+  if (glam) go(glam, bx);
+  else go(bx);
   return hipGetLastError();
 }
 

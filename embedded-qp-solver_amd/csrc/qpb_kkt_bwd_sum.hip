@@ -41,11 +41,21 @@ constexpr int kSumUnroll = 4;  // matrix-core steps (of 4 QPs) whose loads a wav
 // NT = ceil(n / 16); MT = ceil(m / 16), or 0 when gA is not wanted.  The slot
 // holds S as a (16 NT) x (16 NT) row-major matrix, then gA's sum as
 // (16 MT) x (16 NT); parts that are not wanted are not written (nor read).
-template <int NT, int MT>
+// BX (empty, or one int: pass 2 of qpb_solve_range_box_backward): the row stride
+// ms of lam and of the mask words' rows.  It is m everywhere else; in this form
+// m is mg, the rows of G that are summed, gbg is pass 1's unrouted B x mg array
+// and lam and active keep the mg + n rows of the solve: a row < mg feeds the
+// numbers the call on [G; I] feeds for it, and an output element of the
+// matrix-core instruction depends on its own row and column only.
+template <int NT, int MT, class... BX>
 __global__ __launch_bounds__(64) void kkt_bwd_sum_kernel(
     const double *__restrict__ xg, const double *__restrict__ dxg, const double *__restrict__ gbg,
     const double *__restrict__ lamg, const uint32_t *__restrict__ actg, const int32_t *__restrict__ statg,
-    double *__restrict__ slots, int n, int m, long long batch, long long per, long long slot_doubles, int wantH) {
+    double *__restrict__ slots, int n, int m, long long batch, long long per, long long slot_doubles, int wantH,
+    BX... msg) {
+  static_assert(std::is_same_v<void(BX...), void()> || std::is_same_v<void(BX...), void(int)>);
+  int ms = m;
+  if constexpr (sizeof...(BX) == 1) ms = (msg, ...);
   const int l = threadIdx.x, c = l & 15, q = l >> 4;
   const long long kb = (long long)blockIdx.x * per;  // < batch: the plan has no empty slice
   const long long ke = kb + per < batch ? kb + per : batch;
@@ -59,7 +69,7 @@ __global__ __launch_bounds__(64) void kkt_bwd_sum_kernel(
   for (int i = 0; i < MTA; ++i)
 #pragma unroll
     for (int j = 0; j < NT; ++j) G[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-  const int words = (m + 31) / 32;
+  const int words = (ms + 31) / 32;
   // kSumUnroll steps of 4 QPs per trip: every load of the trip is issued before
   // its first matrix-core instruction, so a wave has kSumUnroll steps' loads in
   // flight instead of one (one step per trip waited a full memory latency per
@@ -89,7 +99,7 @@ __global__ __launch_bounds__(64) void kkt_bwd_sum_kernel(
           const int row = 16 * t + c;
           const bool in = row < m;
           const int rc = in ? row : 0;
-          const double gbv = gbg[kc * m + rc], lv = lamg[kc * m + rc];
+          const double gbv = gbg[kc * m + rc], lv = lamg[kc * ms + rc];
           const uint32_t w = actg[kc * words + (rc >> 5)];
           const bool bit = (w >> (rc & 31)) & 1u;
           dl[u][t] = (ok && in) ? -gbv : 0.0;
@@ -216,5 +226,39 @@ extern "C" hipError_t qpb_launch_kkt_bwd_sum(const qpb_desc *d, const double *x,
   const int elems = d->n * d->n + d->m * d->n;
   hipLaunchKernelGGL(qpb::bwd::kkt_bwd_sum_finish_kernel, dim3((unsigned)((elems + 15) / 16)), dim3(256), 0, stream,
                      slots, plan.slots, sd, 16 * nt, d->n, d->m, gH, gA);
+  return hipGetLastError();
+}
+
+// pass 2 of qpb_solve_range_box_backward: the same two launches over the mg rows
+// of G (d->m is mg + n), from pass 1's gf (dx) and its unrouted gbw
+extern "C" hipError_t qpb_launch_kkt_bwd_sum_range_box(const qpb_desc *d, int mg, const double *x, const double *dx,
+                                                       const double *gbw, const double *lam, const uint32_t *active,
+                                                       const int32_t *status, double *slots, double *gH, double *gG,
+                                                       hipStream_t stream) {
+  const qpb::SumPlan plan = qpb::sum_plan(d->batch);
+  const long long sd = qpb::sum_slot_doubles(d->n, mg);
+  const int nt = (d->n + 15) / 16, mt = gG ? (mg + 15) / 16 : 0;
+  auto launch = [&](auto NT, auto MT) {
+    hipLaunchKernelGGL((qpb::bwd::kkt_bwd_sum_kernel<NT(), MT(), int>), dim3((unsigned)plan.slots), dim3(64), 0,
+                       stream, x, dx, gbw, lam, active, status, slots, d->n, mg, (long long)d->batch, plan.per, sd,
+                       gH ? 1 : 0, (int)d->m);
+  };
+  auto with_nt = [&](auto MT) {
+    if (nt == 1) launch(std::integral_constant<int, 1>{}, MT);
+    else launch(std::integral_constant<int, 2>{}, MT);
+  };
+  // (mg + n <= 64 with n >= 1: at most 4 row tiles, as above)
+  switch (mt) {
+    case 0: with_nt(std::integral_constant<int, 0>{}); break;
+    case 1: with_nt(std::integral_constant<int, 1>{}); break;
+    case 2: with_nt(std::integral_constant<int, 2>{}); break;
+    case 3: with_nt(std::integral_constant<int, 3>{}); break;
+    default: with_nt(std::integral_constant<int, 4>{}); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int elems = d->n * d->n + mg * d->n;
+  hipLaunchKernelGGL(qpb::bwd::kkt_bwd_sum_finish_kernel, dim3((unsigned)((elems + 15) / 16)), dim3(256), 0, stream,
+                     slots, plan.slots, sd, 16 * nt, d->n, mg, gH, gG);
   return hipGetLastError();
 }

@@ -138,6 +138,25 @@ QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_dual(const qpb_desc *d, long long str
 QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_sum(const qpb_desc *d, const double *x, const double *dx, const double *gb,
                                                const double *lam, const uint32_t *active, const int32_t *status,
                                                double *slots, double *gH, double *gA, hipStream_t stream);
+// qpb_solve_range_box_backward, pass 1: the BX forms of the same kernels.  d->m
+// counts all rows, mg + n (lam, glam, active and lower in that layout); G is
+// mg x n per QP (strideG 0 or mg n, unread at mg == 0), gG its gradient (NULL
+// where pass 2 sums it).  gb's elements go to gbl / gbu (B x mg) and glb / gub
+// (B x n) by the `lower` bits, and the rows < mg unrouted to gbw (B x mg) for
+// pass 2.  glam, lower and every output may be NULL.
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_range_box(const qpb_desc *d, int mg, long long strideH, long long strideG,
+                                                     const double *H, const double *G, const double *x,
+                                                     const double *lam, const uint32_t *active, const uint32_t *lower,
+                                                     const int32_t *status, const double *gx, const double *glam,
+                                                     double *gH, double *gf, double *gG, double *gbl, double *gbu,
+                                                     double *glb, double *gub, double *gbw, hipStream_t stream);
+// ... pass 2: qpb_launch_kkt_bwd_sum over the rows < mg (d->m is mg + n: the row
+// stride of lam and active; gbw is pass 1's, B x mg).  slots:
+// qpb::sum_plan(batch).slots times qpb::sum_slot_doubles(n, mg) doubles.
+QPB_LAUNCHER hipError_t qpb_launch_kkt_bwd_sum_range_box(const qpb_desc *d, int mg, const double *x, const double *dx,
+                                                         const double *gbw, const double *lam, const uint32_t *active,
+                                                         const int32_t *status, double *slots, double *gH, double *gG,
+                                                         hipStream_t stream);
 // qpb_factor_shared_backward: ONE H and ONE A (NULL at m == 0) into the class's
 // backward buffer (qpb_factor.h, bfct), one small launch of the class's own
 // kernel in its factor form (qpb_kkt_bwd.hip); fstatus may be NULL

@@ -427,6 +427,35 @@ static_assert(route_range_box(16, 16).kernel == route_range(16, 32).kernel &&
               route_range_box(32, 32).kernel == route_range(32, 64).kernel &&
               route_range_box(32, 32).step == route_range(32, 64).step);
 
+// qpb_solve_range_box_backward: the backward route of the materialised problem's
+// shape, m' = mg + n rows, with or without glam and shared operands -- the BX
+// forms sit in route_bwd_dual's two classes, and the call's bits are that
+// call's on [G; I] only in the same class and with the same chunks.
+constexpr Route route_bwd_range_box(int n, int mg) { return route_bwd_dual(n, mg + n); }
+constexpr int kBwdRangeBoxMaxN = kBwdDualMaxN, kBwdRangeBoxMaxRows = kBwdDualMaxM;  // n, and mg + n
+
+static_assert(route_bwd_range_box(16, 16).kernel == Kernel::gi_dense &&
+              route_bwd_range_box(16, 17).kernel == Kernel::gi_wave &&
+              route_bwd_range_box(12, 20).kernel == Kernel::gi_dense &&
+              route_bwd_range_box(1, 0).kernel == Kernel::gi_dense &&
+              route_bwd_range_box(16, 0).kernel == Kernel::gi_dense &&
+              route_bwd_range_box(17, 0).kernel == Kernel::gi_wave &&
+              route_bwd_range_box(32, 32).kernel == Kernel::gi_wave);
+static_assert(route_bwd_range_box(16, 16).step == route_bwd_dual(16, 32).step &&
+              route_bwd_range_box(32, 32).step == route_bwd_dual(32, 64).step &&
+              route_bwd_range_box(16, 16).step == route_bwd(16, 32).step &&
+              route_bwd_range_box(32, 32).step == route_shared_bwd(32, 64).step);
+static_assert(route_bwd_range_box(33, 0).step == 0 && route_bwd_range_box(32, 33).step == 0 &&
+              route_bwd_range_box(16, 49).step == 0 && route_bwd_range_box(129, 32).step == 0);
+static_assert(route_bwd_range_box(kBwdRangeBoxMaxN, kBwdRangeBoxMaxRows - kBwdRangeBoxMaxN).step > 0 &&
+              route_bwd_range_box(kBwdRangeBoxMaxN + 1, 0).step == 0 &&
+              route_bwd_range_box(1, kBwdRangeBoxMaxRows).step == 0);
+// every solve of qpb_solve_range_box has a backward, in the forward's class
+static_assert(kBwdRangeBoxMaxN == kRangeBoxMaxN && kBwdRangeBoxMaxRows == kRangeBoxMaxRows &&
+              route_bwd_range_box(16, 16).kernel == route_range_box(16, 16).kernel &&
+              route_bwd_range_box(16, 17).kernel == route_range_box(16, 17).kernel &&
+              route_bwd_range_box(32, 32).kernel == route_range_box(32, 32).kernel);
+
 // The slice plan of the batch sum (qpb_kkt_bwd_sum.hip): `slots` consecutive
 // slices of `per` QPs, the last one shorter; one wavefront and one workspace
 // slot per slice.  A function of the batch size alone -- not of the device --

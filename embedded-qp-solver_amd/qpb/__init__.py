@@ -131,6 +131,10 @@ _lib.qpb_solve_range_box.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctype
 _lib.qpb_solve_range_box.restype = ctypes.c_int
 _lib.qpb_solve_range_box_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32, ctypes.c_int32] + [_vp] * 13
 _lib.qpb_solve_range_box_host.restype = ctypes.c_int
+_lib.qpb_solve_range_box_backward.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 17
+_lib.qpb_solve_range_box_backward.restype = ctypes.c_int
+_lib.qpb_solve_range_box_backward_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 16
+_lib.qpb_solve_range_box_backward_host.restype = ctypes.c_int
 _lib.qpb_solve_range_factored.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 11
 _lib.qpb_solve_range_factored.restype = ctypes.c_int
 _lib.qpb_solve_range_factored_host.argtypes = [ctypes.POINTER(Desc), ctypes.c_int32] + [_vp] * 10
@@ -771,6 +775,116 @@ def solve_range_box_host(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max
                                        p(ub), p(x), p(lam), p(act), p(low), p(st), p(it))
     _check(rc, "qpb_solve_range_box_host")
     return RangeSolution(x, lam, act, low, st, it)
+
+
+RANGE_BOX_NEED_ALL = ("H", "f", "G", "bl", "bu", "lb", "ub")
+
+
+def _range_box_need_set(need) -> set:
+    need = set(need)
+    if not need or not need <= set(RANGE_BOX_NEED_ALL):
+        raise ValueError(f"need must be a non-empty subset of {RANGE_BOX_NEED_ALL}")
+    return need
+
+
+def solve_range_box_backward(H, G, sol: RangeSolution, gx, glam=None, *, need=RANGE_BOX_NEED_ALL, stream=None):
+    """Gradients of ``solve_range_box`` through its KKT system
+    (qpb_solve_range_box_backward), without ``[G; I]`` in memory: given ``sol``
+    from that call on (H, f, G, bl, bu, lb, ub), the cotangent ``gx = dl/dx``
+    (B, n) and, for a loss that reads the multipliers, ``glam = dl/dlam``
+    (B, mg + n) in ``sol.lam``'s layout, returns ``(gH, gf, gG, gbl, gbu, glb,
+    gub)``: gH and gG in the shapes of H and G (a 2-D one is shared and its
+    gradient is ONE matrix, the sum over the batch), gf, glb, gub (B, n) and gbl,
+    gbu (B, mg).  Every output is, bit for bit, ``solve_backward_dual`` on the
+    materialised ``[G; I]`` -- gG its first mg rows, its gb routed by
+    ``sol.lower``: to the lower bound's array where the row's bit is set, to the
+    upper bound's otherwise, +0.0 in the other.  An entry is None where its name
+    is not in ``need``, and gG at ``G is None``.  ``glam=None`` is the call
+    without it, launch for launch.  n <= 32 and mg + n <= 64."""
+    import torch
+    need = _range_box_need_set(need)
+    if not (H.is_cuda and gx.is_cuda):
+        raise ValueError("qpb.solve_range_box_backward expects CUDA (HIP) tensors; use solve_range_box_backward_host")
+    B, n = gx.shape
+    mg = 0 if G is None else G.shape[-2]
+    m = mg + n
+    w = (m + 31) // 32
+    for t in (H, G, gx, glam, sol.x, sol.lam):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.device != gx.device):
+            raise ValueError("inputs must be contiguous float64 tensors on one CUDA device")
+    if (tuple(H.shape) not in ((n, n), (B, n, n)) or (mg and tuple(G.shape) not in ((mg, n), (B, mg, n)))
+            or tuple(sol.x.shape) != (B, n) or tuple(sol.lam.shape) != (B, m)
+            or (glam is not None and tuple(glam.shape) != (B, m))):
+        raise ValueError("shape mismatch")
+    for name, t in (("active", sol.active), ("lower", sol.lower)):
+        if t is not None and (not t.is_contiguous() or tuple(t.shape) != (B, w) or t.element_size() != 4):
+            raise ValueError(f"sol.{name} must be a contiguous (B, ceil((mg + n)/32)) tensor of 32-bit words")
+    if sol.active is None:
+        raise ValueError("sol.active is required")
+    if sol.lower is None and ("bl" in need or "lb" in need):
+        raise ValueError("sol.lower is required for the gradients of bl and lb")
+    if sol.status is not None and (sol.status.dtype != torch.int32 or not sol.status.is_contiguous()
+                                   or tuple(sol.status.shape) != (B,)):
+        raise ValueError("sol.status must be a contiguous int32 tensor of shape (B,) or None")
+    shared = (SHARED_H if H.dim() == 2 else 0) | (SHARED_A if mg and G.dim() == 2 else 0)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=gx.device)  # noqa: E731
+    gH = new(*H.shape) if "H" in need else None
+    gf = new(B, n) if "f" in need else None
+    gG = new(*G.shape) if mg and "G" in need else None
+    gbl = new(B, mg) if "bl" in need else None
+    gbu = new(B, mg) if "bu" in need else None
+    glb = new(B, n) if "lb" in need else None
+    gub = new(B, n) if "ub" in need else None
+    outs = (gH, gf, gG, gbl, gbu, glb, gub)
+    if all(t is None or not t.numel() for t in outs):
+        return outs  # mg == 0 and only G / bl / bu wanted
+    opt = lambda t: _ptr(t) if t is not None and t.numel() else None  # noqa: E731
+    d = Desc(n, mg, B, 0, 0, 0.0)
+    rc = _lib.qpb_solve_range_box_backward(ctypes.byref(d), shared, _ptr(H), opt(G), _ptr(sol.x), _ptr(sol.lam),
+                                           _ptr(sol.active), opt(sol.lower), opt(sol.status), _ptr(gx), opt(glam),
+                                           opt(gH), opt(gf), opt(gG), opt(gbl), opt(gbu), opt(glb), opt(gub),
+                                           _stream_ptr(stream))
+    _check(rc, "qpb_solve_range_box_backward")
+    return outs
+
+
+def solve_range_box_backward_host(H, G, sol: RangeSolution, gx, glam=None, *, need=RANGE_BOX_NEED_ALL):
+    """numpy in / numpy out (qpb_solve_range_box_backward_host): ``solve_range_box_backward`` with host arrays."""
+    import numpy as np
+    need = _range_box_need_set(need)
+    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+    H, G, gx, glam, x, lam = (c(a) for a in (H, G, gx, glam, sol.x, sol.lam))
+    B, n = gx.shape
+    mg = 0 if G is None else G.shape[-2]
+    m = mg + n
+    w = (m + 31) // 32
+    u32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a).astype(np.uint32))  # noqa: E731
+    act, low = u32(sol.active), u32(sol.lower)
+    shared = (SHARED_H if H.ndim == 2 else 0) | (SHARED_A if mg and G.ndim == 2 else 0)
+    if (H.shape not in ((n, n), (B, n, n)) or (mg and G.shape not in ((mg, n), (B, mg, n))) or x.shape != (B, n)
+            or lam.shape != (B, m) or act is None or act.shape != (B, w) or (low is not None and low.shape != (B, w))
+            or (glam is not None and glam.shape != (B, m))):
+        raise ValueError("shape mismatch")
+    if low is None and ("bl" in need or "lb" in need):
+        raise ValueError("sol.lower is required for the gradients of bl and lb")
+    st = None if sol.status is None else np.ascontiguousarray(sol.status, dtype=np.int32)
+    gH = np.zeros(H.shape) if "H" in need else None
+    gf = np.zeros((B, n)) if "f" in need else None
+    gG = np.zeros(G.shape) if mg and "G" in need else None
+    gbl = np.zeros((B, mg)) if "bl" in need else None
+    gbu = np.zeros((B, mg)) if "bu" in need else None
+    glb = np.zeros((B, n)) if "lb" in need else None
+    gub = np.zeros((B, n)) if "ub" in need else None
+    outs = (gH, gf, gG, gbl, gbu, glb, gub)
+    if all(t is None or not t.size for t in outs):
+        return outs
+    d = Desc(n, mg, B, 0, 0, 0.0)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+    rc = _lib.qpb_solve_range_box_backward_host(ctypes.byref(d), shared, p(H), p(G), p(x), p(lam), p(act), p(low),
+                                                p(st), p(gx), p(glam), p(gH), p(gf), p(gG), p(gbl), p(gbu), p(glb),
+                                                p(gub))
+    _check(rc, "qpb_solve_range_box_backward_host")
+    return outs
 
 
 def solve_range_factored(F: SharedFactor, f, bl, bu, meq: int = 0, *, max_iter: int = 0, feas_tol: float = 0.0,

@@ -38,8 +38,11 @@ factored one in the same way.
 
 ``solve_range_box(H, f, G, bl, bu, lb, ub, meq)`` is ``qpb.solve_range_box`` --
 those rows beside variable bounds, no identity rows in G -- with gradients for
-H, f, G and the four bounds.  Only the backward assembles ``[G; I]``, for
-``qpb.solve_backward`` (or the shared one); a native backward is a follow-up.
+H, f, G and the four bounds.  The backward is ``qpb.solve_range_box_backward``:
+neither pass builds ``[G; I]``, and the gradients are bit for bit those of
+``qpb.solve_backward`` (or the shared one) on it.  ``solve_range_box_dual``
+returns ``(x, lam, status)`` with lam differentiable as well, in the manner of
+``solve_range_dual``.
 
 ``solve_dual(H, f, A, b, meq)`` and ``solve_range_dual(H, f, A, bl, bu, meq)``
 return ``(x, lam, status)`` with x AND lam differentiable: the backward is
@@ -195,8 +198,6 @@ class RangeBoxQPFunction(torch.autograd.Function):
         H, f, G, bl, bu, lb, ub = (c(t) for t in (H, f, G, bl, bu, lb, ub))
         # above n = 32 or mg + n = 64 this raises QPBError(ERR_UNSUPPORTED)
         sol = qpb.solve_range_box(H, f, G, bl, bu, lb, ub, meq, max_iter=max_iter, feas_tol=feas_tol)
-        ctx.prefactor = False
-        ctx.mg = 0 if G is None else G.shape[-2]
         ctx.has = (True, True, G is not None) + tuple(t is not None for t in (bl, bu, lb, ub))
         ctx.save_for_backward(H, G, sol.x, sol.lam, sol.active, sol.lower, sol.status)
         ctx.mark_non_differentiable(sol.status)
@@ -204,44 +205,46 @@ class RangeBoxQPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, _gstatus):
-        H, G, x, lam, active, lower, status = ctx.saved_tensors
-        want = [w and has for w, has in zip(ctx.needs_input_grad[:7], ctx.has)]
-        wanted = [k for k, w in zip("HfA", want[:3]) if w] + (["b"] if any(want[3:]) else [])
-        if not wanted:
-            return (None,) * 10
-        # the materialised A' = [G; I] exists here only: (mg + n, n) for one G (or
-        # none), B x (mg + n) x n for a batched one
-        B, n = x.shape
-        mg = ctx.mg
-        eye = torch.eye(n, dtype=x.dtype, device=x.device)
-        if G is None:
-            A = eye
-        elif G.dim() == 2:
-            A = torch.cat([G, eye], dim=0)
-        else:
-            A = torch.cat([G, eye.expand(B, n, n)], dim=1)
-        ctx.shared = H.dim() == 2 or A.dim() == 2
-        sol = qpb.Solution(x, lam, active, status, None)
-        gH, gf, gA, gb = _backward(ctx, H, A.contiguous(), sol, gx.contiguous(), wanted)
-        gG = None if gA is None else gA[..., :mg, :]
-        gbl = gbu = glb = gub = None
-        if gb is not None:
-            # as solve_range routes its gb: an element goes to the lower bound where
-            # the `lower` bit is set (never on an equality), to the upper one elsewhere;
-            # columns < mg are the rows', the others the variables'
-            rows = torch.arange(mg + n, device=gb.device)
-            low = ((lower[:, rows // 32] >> (rows % 32)) & 1).bool()
-            zero = torch.zeros_like(gb)
-            to_lo, to_hi = torch.where(low, gb, zero), torch.where(low, zero, gb)
-            if want[3]:
-                gbl = to_lo[:, :mg]
-            if want[4]:
-                gbu = to_hi[:, :mg]
-            if want[5]:
-                glb = to_lo[:, mg:]
-            if want[6]:
-                gub = to_hi[:, mg:]
-        return gH, gf, gG, gbl, gbu, glb, gub, None, None, None
+        grads = _range_box_backward(ctx, gx, None)
+        return (None,) * 10 if grads is None else grads + (None, None, None)
+
+
+_RANGE_BOX_NAMES = ("H", "f", "G", "bl", "bu", "lb", "ub")
+
+
+def _range_box_backward(ctx, gx, glam):
+    """The seven gradients of a range-box forward (None where not wanted), or None
+    when none is: ``qpb.solve_range_box_backward`` on the saved solve, on torch's
+    current stream.  An unused lam arrives as None and takes the call without
+    glam, an unused x is a zero cotangent."""
+    H, G, x, lam, active, lower, status = ctx.saved_tensors
+    wanted = [k for k, w, has in zip(_RANGE_BOX_NAMES, ctx.needs_input_grad[:7], ctx.has) if w and has]
+    if not wanted or (gx is None and glam is None):
+        return None
+    sol = qpb.RangeSolution(x, lam, active, lower, status, None)
+    gx = torch.zeros_like(x) if gx is None else gx.contiguous()
+    return qpb.solve_range_box_backward(H, G, sol, gx, None if glam is None else glam.contiguous(), need=wanted)
+
+
+class RangeBoxDualQPFunction(torch.autograd.Function):
+    """(x*, lam*)(H, f, G, bl, bu, lb, ub) of ``RangeBoxQPFunction``'s problem, lam signed, (B, mg + n)."""
+
+    @staticmethod
+    def forward(ctx, H, f, G, bl, bu, lb, ub, meq, max_iter, feas_tol):
+        c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+        H, f, G, bl, bu, lb, ub = (c(t) for t in (H, f, G, bl, bu, lb, ub))
+        # above n = 32 or mg + n = 64 this raises QPBError(ERR_UNSUPPORTED)
+        sol = qpb.solve_range_box(H, f, G, bl, bu, lb, ub, meq, max_iter=max_iter, feas_tol=feas_tol)
+        ctx.has = (True, True, G is not None) + tuple(t is not None for t in (bl, bu, lb, ub))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(H, G, sol.x, sol.lam, sol.active, sol.lower, sol.status)
+        ctx.mark_non_differentiable(sol.status)
+        return sol.x, sol.lam, sol.status
+
+    @staticmethod
+    def backward(ctx, gx, glam, _gstatus):
+        grads = _range_box_backward(ctx, gx, glam)
+        return (None,) * 10 if grads is None else grads + (None, None, None)
 
 
 def _backward_dual(ctx, H, A, x, lam, active, status, gx, glam, wanted):
@@ -453,16 +456,29 @@ def solve_range_box(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max_iter
     """Differentiable batched solve with two-sided rows beside variable bounds
     (``qpb.solve_range_box`` with gradients): returns ``(x, status)``; ``x``
     carries gradients to whichever of H, f, G, bl, bu, lb and ub require them.
-    The forward never builds ``[G; I]``.  The backward does, inside
-    ``backward()`` only -- B x (mg+n) x n for a batched G, (mg+n) x n for a 2-D
-    one -- and runs ``qpb.solve_backward`` (``qpb.solve_shared_backward`` with a
-    2-D H or G) on it: ``G.grad`` is its first mg rows (one summed (mg, n)
-    matrix for a 2-D G), and its ``gb`` goes to ``bl`` / ``bu`` / ``lb`` / ``ub`` by
-    the ``lower`` bits exactly as ``solve_range`` routes it.  A bound passed as
-    None gets no gradient.  A native backward without ``[G; I]`` is a follow-up.
+    Neither pass builds ``[G; I]``: the backward is
+    ``qpb.solve_range_box_backward``, bit for bit ``qpb.solve_backward``
+    (``qpb.solve_shared_backward`` with a 2-D H or G) on it -- ``G.grad`` is its
+    first mg rows (one summed (mg, n) matrix for a 2-D G), and its ``gb`` goes to
+    ``bl`` / ``bu`` / ``lb`` / ``ub`` by the ``lower`` bits exactly as
+    ``solve_range`` routes it.  A bound passed as None gets no gradient.
     n <= 32 and mg + n <= 64: above that the forward raises
     ``QPBError(ERR_UNSUPPORTED)``."""
     return RangeBoxQPFunction.apply(H, f, G, bl, bu, lb, ub, int(meq), int(max_iter), float(feas_tol))
+
+
+def solve_range_box_dual(H, f, G, bl, bu, lb=None, ub=None, meq: int = 0, *, max_iter: int = 0,
+                         feas_tol: float = 0.0):
+    """``solve_range_box`` that also returns the signed multipliers,
+    differentiably: returns ``(x, lam, status)`` with ``lam`` (B, mg + n) in
+    ``qpb.solve_range_box``'s layout and convention (the rows first, then variable
+    j at mg + j; >= 0 at an upper bound, <= 0 at a lower one).  The backward is
+    ``qpb.solve_range_box_backward`` on the two cotangents, routed to the four
+    bounds exactly as in ``solve_range_box``.  A bound passed as None gets no
+    gradient.  A loss that does not read ``lam`` gets ``solve_range_box``'s
+    gradients bit for bit, and one that does not read ``x`` has gx = 0.
+    n <= 32 and mg + n <= 64."""
+    return RangeBoxDualQPFunction.apply(H, f, G, bl, bu, lb, ub, int(meq), int(max_iter), float(feas_tol))
 
 
 def solve_box(H, f, lb=None, ub=None, *, max_iter: int = 0, feas_tol: float = 0.0, prefactor: bool = False):

@@ -636,8 +636,8 @@ int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
  * bounds (lb_j > ub_j beyond the threshold is QPB_INFEASIBLE from the set-up); a
  * pinned variable lb_j == ub_j as a zero-width row; lower a subset of active; a
  * QP's outputs depend on its own inputs only; the default max_iter is
- * 4 (n + m') + 8.  active and lam go to qpb_solve_backward together with a
- * materialised A' (a native backward without A' is a follow-up).
+ * 4 (n + m') + 8.  lam, active and lower go to qpb_solve_range_box_backward,
+ * below, unchanged: the gradients without A' as well.
  * What the call saves is A' itself: the identity's rows are made in registers by
  * the BX forms of the range kernels (qpb_gi.hip, qpb_gi_wave.hip), neither
  * allocated nor filled by the caller, nor read by the kernel, nor gathered again
@@ -651,8 +651,7 @@ int qpb_solve_range_host(const qpb_desc *desc, int32_t meq, int32_t shared,
  * Limits: the two wavefront-level classes by the materialised shape, n <= 16
  * with mg + n <= 32 and n <= 32 with mg + n <= 64.  Follow-ups: the n <= 128
  * Gram class, a factored form (with H and G shared, qpb_factor_shared on
- * [G; I] serves qpb_solve_range_factored today), QPB_FLAG_MIXED and a native
- * backward.
+ * [G; I] serves qpb_solve_range_factored today) and QPB_FLAG_MIXED.
  * Device pointers; asynchronous on `stream`. */
 int qpb_solve_range_box(const qpb_desc *desc, int32_t meq, int32_t shared,
 			const double *H, const double *f, const double *G,
@@ -668,6 +667,74 @@ int qpb_solve_range_box_host(const qpb_desc *desc, int32_t meq, int32_t shared,
 			     const double *lb, const double *ub, double *x,
 			     double *lam, uint32_t *active, uint32_t *lower,
 			     int32_t *status, int32_t *iters);
+
+/* The backward of qpb_solve_range_box: the gradients of a loss l with respect to
+ * H, f, G and the four bound arrays from gx = dl/dx and, where it is not NULL,
+ * glam = dl/dlam, without A' = [G; I] in memory.  desc->m is mg, as in the
+ * forward; lam, active, lower and glam are in that call's layouts on
+ * m' = mg + n rows (row i at i, variable j at mg + j, ceil(m' / 32) words).
+ * `shared` is the QPB_SHARED_H | QPB_SHARED_A bit set.  There is no meq: an
+ * equality row is a row whose bit is set in `active` and clear in `lower`.
+ * Specification: the materialised problem.  Let (gH', gf', gA', gb') be what
+ * qpb_solve_backward_dual(shared, H, A' = [G; I], x, lam, active, status, gx,
+ * glam) writes on m' rows (with glam == NULL that call is
+ * qpb_solve_shared_backward, with shared == 0 qpb_solve_backward).  Then, bit
+ * for bit:
+ *   gH, gf   gH' and gf'; a shared H gives ONE n x n matrix, symmetric bit for bit
+ *   gG       rows 0 .. mg-1 of gA': mg x n per QP, or with QPB_SHARED_A ONE
+ *            mg x n matrix, the first mg rows of that call's summed gA'.  The
+ *            identity rows' gradient is neither computed for storing nor stored.
+ *   gbl, gbu (mg per QP), glb, gub (n per QP)   gb' routed by the `lower` bits:
+ *            an element goes to the lower-bound array where the row's bit is
+ *            set and to the upper-bound array otherwise; the other array gets
+ *            +0.0 (selected, never multiplied).  A `lower` bit on a row whose
+ *            `active` bit is clear routes that row's zero.
+ * Every sentence of qpb_solve_backward's contract therefore holds unchanged:
+ * weakly active and dependent rows (a row of G equal to +-e_j beside variable
+ * j's bit is the natural dependent row; the test runs in row order, so the skip
+ * lands on the variable), masks with more than n bits, bits >= m' ignored, lam
+ * and glam outside the active set ignored (NaN included), zeros for a QP whose
+ * status is not QPB_OK and its exact-zero share of a sum, status NULL, every
+ * element of every non-NULL output written and nothing else, the summed outputs'
+ * bits a function of the inputs and (n, mg, batch) only.
+ * mg == 0: G may be NULL and gG is ignored.  Each of the seven outputs may be
+ * NULL; at least one must be given.  lower may be NULL only when gbl and glb
+ * both are: every routed element then goes to the upper arrays.
+ * The kernels are the BX forms of qpb_solve_backward's (qpb_kkt_bwd.hip), in the
+ * class of the materialised shape: a unit row is made in registers where the
+ * other forms load a row of A, and nothing differs from the factorisation on.
+ * A summed gG or gH takes the second pass of qpb_solve_shared_backward over the
+ * rows of G (workspace: the slots, B n doubles where gf is NULL, B mg where gG
+ * is summed).
+ * Errors, in order: the descriptor as qpb_solve, with m = mg; desc->flags != 0 or
+ * a bit of `shared` outside QPB_SHARED_H | QPB_SHARED_A, QPB_ERR_INVALID_ARG;
+ * n > 32 or mg + n > 64 QPB_ERR_UNSUPPORTED; batch == 0 returns 0 before the
+ * pointers are looked at; missing pointers QPB_ERR_INVALID_ARG (H, x, lam,
+ * active and gx always; G with mg > 0; lower as above; one output); a missing
+ * device last.
+ * Follow-ups: a tangent helper, a form on a factor buffer, T directions per QP
+ * and the n <= 128 Gram class.
+ * Device pointers; asynchronous on `stream`. */
+int qpb_solve_range_box_backward(const qpb_desc *desc, int32_t shared,
+				 const double *H, const double *G,
+				 const double *x, const double *lam,
+				 const uint32_t *active, const uint32_t *lower,
+				 const int32_t *status, const double *gx,
+				 const double *glam, double *gH, double *gf,
+				 double *gG, double *gbl, double *gbu,
+				 double *glb, double *gub, void *stream);
+
+/* Same with host pointers, as qpb_solve_backward_host (a shared operand and its
+ * gradient are one matrix). */
+int qpb_solve_range_box_backward_host(const qpb_desc *desc, int32_t shared,
+				      const double *H, const double *G,
+				      const double *x, const double *lam,
+				      const uint32_t *active,
+				      const uint32_t *lower,
+				      const int32_t *status, const double *gx,
+				      const double *glam, double *gH,
+				      double *gf, double *gG, double *gbl,
+				      double *gbu, double *glb, double *gub);
 
 /* qpb_solve_range(shared = QPB_SHARED_H | QPB_SHARED_A) without the per-QP
  * set-up: two-sided rows on a buffer of qpb_factor_shared for (desc->n,
